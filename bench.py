@@ -7,14 +7,20 @@ NSFF, 64 coarse + 64 importance samples (-> 192 fine points per ray), train-mode
 the device.  value = n_gpus * 1024 * (64+64) * steps / time  ("nominal" ray-samples, the
 accounting of SURVEY.md 8d).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 starts N ranks itself (one process per GPU, RCCL) when it was not already started by
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`` (both work).
 Multi-GPU is weak scaling: every rank renders its own 1024 rays (no data-path collective)
 and the step ends with ONE RCCL all-gather of the rendered pixels (rgb_fine, depth_fine).
 
-Extra objects on the JSON line:
+A plain run sets up, settles the clocks, warms up, times the K steps and prints the line: nothing else runs on the GPU or
+the host.  ``--dump-outputs DIR`` writes what the last timed step returned (rank 0) as DIR/<name>.npy; the generator is
+reseeded (and a training run's weights and Adam state restored) after the time-sized settle phase, so the same arguments
+give the same inputs to that step in every run and two builds can be compared output for output (the render and frame
+workloads repeat bit for bit; training steps differ from process to process in their last bits, and more after several).
+
+Extra objects on the JSON line, measured only with ``--full``:
   roofline     -- the field (MLP) kernel: algorithmic FLOPs (2*MACs, unpadded K)
                   per launch / average launch duration from HIP events recorded on the
                   launch stream inside the timed region, against the dense MFMA peak of the dtype.
@@ -266,6 +272,9 @@ class Bench:
 
 LAST_STEP_EVENTS = []        # sorted per-step HIP-event milliseconds of the most recent timed() on this rank
 LAST_HOST_ISSUE_MS = [None]  # host milliseconds per step spent ISSUING the most recent timed() loop (before any synchronize)
+LAST_OUTPUT = [None]         # what the last timed step of the most recent timed() returned (for --dump-outputs)
+DUMP_SEED = 0
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def median_step_ms():
@@ -276,11 +285,12 @@ def median_step_ms():
     return ev[n // 2] if n % 2 else 0.5 * (ev[n // 2 - 1] + ev[n // 2])
 
 
-def timed(step, steps, warmup, world, device, prof=False, bench=None):
+def timed(step, steps, warmup, world, device, prof=False, bench=None, keep_output=False):
     """W untimed steps, then exactly K steps bracketed by barrier + synchronize; returns (seconds [max over ranks],
     field-kernel (launches, ms, flops) from HIP events on the launch stream when prof, per-rank report).  The report
     (`bench` given and a process group alive) holds every rank's own seconds for the K steps and the milliseconds it
-    spent in the pixel all-gather: rank 0 prints their min / max, so a scaling line explains itself."""
+    spent in the pixel all-gather: rank 0 prints their min / max, so a scaling line explains itself.  keep_output: the last
+    step's return value is kept in LAST_OUTPUT."""
     import torch.distributed as dist
     from nsff_pl_amd import _lib
     gpu = device.type == "cuda"
@@ -309,7 +319,10 @@ def timed(step, steps, warmup, world, device, prof=False, bench=None):
     for i in range(steps):
         if gpu:
             marks[i].record()
-        step()
+        if keep_output and i == steps - 1:
+            LAST_OUTPUT[0] = step()
+        else:
+            step()
     LAST_HOST_ISSUE_MS[0] = (time.perf_counter() - t0) / max(steps, 1) * 1e3
     if bench is not None:
         bench.finish()                          # the last step's overlapped pixel gather joins inside the timed region
@@ -338,6 +351,40 @@ def timed(step, steps, warmup, world, device, prof=False, bench=None):
                     "note": "each rank's own time for the K steps (host clock around its loop + device synchronize, before the "
                             "closing barrier) and the part of it inside the pixel all-gather (HIP events around the collective)"}
     return elapsed, kern, per_rank
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: every tensor of a step's return value (nested dicts / lists / tuples) as DIR/<name>.npy -- float64 stays
+    float64, every other dtype becomes float32.  Above DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample
+    of the rows of its first dimension."""
+    import re
+    import numpy as np
+    arrays = {}
+
+    def walk(name, v):
+        if isinstance(v, dict):
+            items = v.items()
+        elif isinstance(v, (list, tuple)):
+            items = enumerate(v)
+        else:
+            if torch.is_tensor(v):
+                t = v.detach().to(torch.float64 if v.dtype == torch.float64 else torch.float32)
+                arrays[re.sub(r"[^A-Za-z0-9_.-]", "_", name or "output")] = t.cpu().numpy()
+            return
+        for k, x in items:
+            walk(f"{name}.{k}" if name else str(k), x)
+    walk("", out)
+    rows = [name for name, a in arrays.items() if a.ndim and len(a) > 1]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        fixed = total - sum(arrays[name].nbytes for name in rows)
+        for name in rows:
+            n = len(arrays[name])
+            keep = np.random.default_rng(DUMP_SEED).choice(n, n * (DUMP_LIMIT_BYTES - fixed) // (total - fixed), replace=False)
+            arrays[name] = arrays[name][np.sort(keep)]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 NOMINAL_GHZ = 2.4            # the clock the dense peaks of MI355X_MICROARCH.md are quoted at
@@ -624,11 +671,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the field-launch roofline "
+                         "(HIP events around the field launches of the timed steps) and the aux block")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--settle-ms", type=float, default=600.0,
                     help="untimed steps run for this long BEFORE the W warm-up steps: the part comes out of its idle state (95 MHz "
                          "while the CPU baseline runs) and its power management settles; 0 = none.  Reported in config.settle_ms")
-    ap.add_argument("--no-aux", action="store_true", help="skip the aux block (other configurations after the headline)")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the aux block (other configurations after the headline)")
     ap.add_argument("--precision", default=os.environ.get("NSFF_PRECISION", "f16x3"), choices=["f32", "f16x3"],
                     help="arithmetic of the dense layers; f32 (exact fp32 MFMA) and f16x3 (three f16 products per MAC, the "
                          "default) pass the same 1e-4 parity tests")
@@ -663,13 +715,16 @@ def main():
 
     bench = Bench(rank, world, device, graph=args.graph and args.workload == "train", standin=args.standin)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.standin:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.standin:
         cpu = cpu_baseline(bench.cfg, bench.models, bench.emb)
     if not args.standin:
         bench.to_device()
     step = {"render": bench.render_step, "train": bench.train_step,
             "eval": lambda: bench.frame_steps(False), "eval_interp": lambda: bench.frame_steps(True)}[args.workload]()
 
+    # a training step changes the weights, and two processes' steps differ in their last bits: a dump run restores the
+    # trainer's state from before its first step once the settle phase is over
+    keep = bench.trainer.checkpoint() if args.dump_outputs and args.workload == "train" else None
     if args.settle_ms > 0 and not args.standin:
         # the same number of settle steps on every rank (a step may end in a collective): sized from ten steps on this rank
         t0 = time.perf_counter()
@@ -685,12 +740,22 @@ def main():
             step()
         bench.finish()
         torch.cuda.synchronize()
-    elapsed, kern, per_rank = timed(step, args.steps, args.warmup, world, device, prof=not args.standin, bench=bench)
+    if args.dump_outputs:
+        # the dumped step's inputs follow from the arguments alone, whatever number of steps the settle phase took
+        if keep is not None:
+            bench.trainer.load_checkpoint(keep, strict=True)
+        torch.manual_seed(DUMP_SEED)
+    elapsed, kern, per_rank = timed(step, args.steps, args.warmup, world, device, prof=args.full and not args.standin, bench=bench,
+                                    keep_output=bool(args.dump_outputs))
     median_ms = median_step_ms()               # (of the headline's steps: the aux block below times other things)
     host_issue_ms = LAST_HOST_ISSUE_MS[0]
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(LAST_OUTPUT[0], args.dump_outputs)
+        LAST_OUTPUT[0] = None
 
     aux = None
-    if rank == 0 and world == 1 and args.workload == "render" and not args.no_aux and not args.standin:
+    if args.full and rank == 0 and world == 1 and args.workload == "render" and not args.no_aux and not args.standin:
         aux = aux_block(bench, args)
 
     if rank == 0:
@@ -709,7 +774,7 @@ def main():
                                    "perturb=1 noise_std=1, 8x256 MLPs, N_tau=48, all 47 outputs on device.  `value` is "
                                    "render_rays' throughput with autograd DISABLED (the train-mode FLAGS, inference launches: "
                                    "nothing kept for a backward pass); what a trainer's forward costs is aux.train_forward, "
-                                   "the whole training step aux.train_ms_per_step_*",
+                                   "the whole training step aux.train_ms_per_step_* (both with --full)",
                        "settle_ms": args.settle_ms,
                        "rays_per_gpu": N_RAYS, "N_samples": N_SAMPLES, "N_importance": N_IMPORTANCE,
                        "parallelism": f"ray-shard x{world}, pixel all-gather" if bench.live else "single GPU",
@@ -720,7 +785,7 @@ def main():
         if args.standin:
             line["data"] = "STAND-IN (CPU plumbing check, not a measurement)"
             line["config"] = {"workload": "stand-in"}
-        else:
+        elif args.full:
             line["roofline"] = roofline_block(args.precision, kern)
         if args.workload in ("eval", "eval_interp"):
             n_px = bench.frame["H"] * bench.frame["W"]

@@ -70,6 +70,40 @@ def test_bench_single_process_and_torchrun_forms():
     assert "per_rank" not in _json_lines(one.stdout)[0]          # plain `python bench.py`: no group, no collective
 
 
+def test_bench_dumps_what_the_last_step_returned(tmp_path):
+    """--dump-outputs DIR: one .npy per array the timed step returns (float32 here), the same in every run."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--standin",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, env=_env())
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len(_json_lines(p.stdout)) == 1
+        runs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert sorted(runs[0]) == ["depth_fine.npy", "rgb_fine.npy"]
+    for f, a in runs[0].items():
+        assert a.dtype == np.float32 and a.shape[0] == 1024 and np.array_equal(a, runs[1][f])
+
+
+def test_dump_keeps_a_fixed_sample_of_rows_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    out = {"train/loss": torch.tensor(0.5), "rows": [torch.randn(4096, 128).half(), torch.arange(4096, dtype=torch.float64)]}
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["rows.0.npy", "rows.1.npy", "train_loss.npy"]
+    got = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert 0 < sum(a.nbytes for a in got.values()) <= 1 << 20
+    assert got["rows.0.npy"].dtype == np.float32 and got["rows.1.npy"].dtype == np.float64 and got["train_loss.npy"] == 0.5
+    assert all(np.array_equal(a, np.load(tmp_path / "b" / n)) for n, a in got.items())
+    rows = got["rows.1.npy"].astype(np.int64)                  # the same rows of every array
+    assert 0 < len(rows) < 4096 and np.array_equal(got["rows.0.npy"], out["rows"][0][rows].float().numpy())
+
+
 def test_launcher_propagates_a_failing_rank():
     from nsff_pl_amd import dist as ndist
     code = "import os,sys,time; r=int(os.environ['RANK']); sys.exit(3) if r==1 else time.sleep(30)"

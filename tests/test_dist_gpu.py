@@ -163,7 +163,7 @@ def test_bench_in_its_torchrun_form_on_one_gpu(hip_lib):
                                                             ndist.INIT_ENV)}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29671", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--no-aux", "--no-cpu-baseline"]
+           "--full", "--no-aux", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
@@ -191,7 +191,7 @@ def test_bench_other_workloads_in_their_torchrun_form_on_one_gpu(extra, hip_lib)
                                                             ndist.INIT_ENV)}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29673", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--no-aux", "--no-cpu-baseline", "--settle-ms", "0"] + extra
+           "--full", "--no-aux", "--no-cpu-baseline", "--settle-ms", "0"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]

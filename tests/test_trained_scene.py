@@ -11,6 +11,7 @@ import scenes
 import nsff_pl_amd as A
 
 N_RAYS, STEPS = 1024, 300
+LAST = 50                       # what a run reached: the mean loss of its last LAST steps, the mean PSNR every 10 steps in them
 
 
 def _render(models, emb, rays, ts, cfg, precision):
@@ -55,26 +56,36 @@ def test_student_fits_the_teacher_and_precisions_agree_on_trained_weights(hip_li
             batch["rgbs"], batch["rays"], batch["ts"] = target.clone(), rays, ts
             before = _psnr(_render(student, emb_s, rays, ts, cfg, "f16x3")["rgb_fine"], target)
             torch.manual_seed(1234)                                      # (the stratified-sampling draws of the 300 steps)
-            for _ in range(STEPS):
+            losses, psnrs = [], []
+            for i in range(STEPS):
                 log = tr.step(batch)
-            loss = float(log["train/loss"])
-            assert loss == loss and abs(loss) < float("inf")
+                if i >= STEPS - LAST:
+                    losses.append(float(log["train/loss"]))
+                    if (STEPS - 1 - i) % 10 == 0:
+                        with torch.random.fork_rng(devices=[DEV]):       # (the evaluation leaves the training draws alone)
+                            psnrs.append(_psnr(_render(student, emb_s, rays, ts, cfg, "f16x3")["rgb_fine"], target))
+            assert all(l == l and abs(l) < float("inf") for l in losses)
+            loss = sum(losses) / LAST
         finally:
             A.config.set_grad_precision("f16")
         out = {p: _render(student, emb_s, rays, ts, cfg, p) for p in ("f32", "f16x3")}
-        after = _psnr(out["f16x3"]["rgb_fine"], target)
+        assert len(psnrs) == LAST // 10                                  # steps 260, 270, ..., 300
+        after = sum(psnrs) / len(psnrs)
         # measured: 18.3 dB untrained -> 33.9 dB after 300 steps (37-40 dB after 600)
         assert after > before + 10.0 and after > 28.0, (mode, before, after)
         for key in ("rgb_fine", "depth_fine"):
             assert rel(out["f16x3"][key], out["f32"][key]) <= 1e-4, key          # measured 7e-7 / 1e-6: the parity bar on trained weights
         assert abs(_psnr(out["f16x3"]["rgb_fine"], target) - _psnr(out["f32"]["rgb_fine"], target)) < 0.01
         result[mode] = (before, after, loss)
-    print("\nbackward arithmetic   PSNR before -> after %d steps   final loss" % STEPS)
+    print("\nbackward arithmetic   PSNR before -> after %d steps (mean of the last %d)   mean loss of the last %d steps"
+          % (STEPS, LAST // 10, LAST))
     for mode, (b, a_, l) in result.items():
         print(f"  {mode:6s}              {b:6.2f} -> {a_:6.2f} dB                {l:.6f}")
     # (two training runs diverge in their digits after a few steps whatever the arithmetic -- and a run does not repeat itself to
     #  the digit from process to process either; what they reach must not differ.  Measured, two processes: one product 18.29 ->
     #  33.10 / 33.25 dB, last step's loss 0.002716 / 0.003208; three products 18.29 -> 34.47 / 33.67 dB, 0.002709 / 0.002566 -- the
-    #  PSNR and the loss of a single step wander by a dB / 20 % that late in such a run)
+    #  PSNR and the loss of a single step wander by a dB / 20 % that late in such a run.  Single points have failed both bounds: last
+    #  steps' losses 0.004443 / 0.002441, final PSNRs 29.63 / 33.83 dB; within one run the PSNR every 10 steps of the last 50 read
+    #  32.64 33.01 30.35 31.11 32.88 -- hence the means over the last LAST steps: 32.0 / 32.9 dB, 0.00423 / 0.00306 in that run)
     assert abs(result["f16"][1] - result["f16x3"][1]) < 2.5, result
     assert abs(result["f16"][2] - result["f16x3"][2]) < 0.5 * result["f16x3"][2], result

@@ -7,12 +7,15 @@ and between the kernel's entry and the asm no compiler code may leave a value in
 the asm (the clobber list guarantees it; the audit reports the count of compiler instructions and the descriptor fields).
 No compiler instruction of the kernel may touch an accumulation register: the first eight weight slots are in flight or resident
 in front of the body and (a persistent workgroup's tile loop: requested by the previous tile's B16LP phase) behind it."""
+import os
 import re
 import subprocess
 import sys
+import tempfile
 
 src = sys.argv[1] if len(sys.argv) > 1 else "nsff_pl_amd/csrc/field_h3.hip"
-out = "/tmp/field_h3_audit.s"
+tmp = tempfile.TemporaryDirectory()          # (a private directory: a fixed file name fails once another user's run owns it)
+out = os.path.join(tmp.name, "field_h3_audit.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, src],
                       stderr=subprocess.DEVNULL)
 txt = open(out).read()

@@ -6,12 +6,15 @@ no scratch, 512 registers per lane available (one wave per SIMD: launch_bounds(2
 a loop over the workgroup's items, and what the compiler keeps across it (the item bookkeeping, the thread index, kernel
 arguments) can only live in v0..v23, s0..s39 -- the statement's clobber list says so -- or in lanes of such a VGPR (SGPR spills:
 allowed; VGPR spills and scratch: not)."""
+import os
 import re
 import subprocess
 import sys
+import tempfile
 
 src = sys.argv[1] if len(sys.argv) > 1 else "nsff_pl_amd/csrc/field_bwd.hip"
-out = "/tmp/field_bwd_audit.s"
+tmp = tempfile.TemporaryDirectory()          # (a private directory: a fixed file name fails once another user's run owns it)
+out = os.path.join(tmp.name, "field_bwd_audit.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, src],
                       stderr=subprocess.DEVNULL)
 txt = open(out).read()
