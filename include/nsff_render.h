@@ -659,6 +659,46 @@ typedef struct {
 } NsffFlowGradArgs;
 int nsff_flow_grad(const NsffFlowGradArgs* args, void* stream);
 
+/* ---- SSIM metric and SSIM-driven ray sampling (reference metrics.py:19-33 over kornia 0.5.4's ssim_loss; train.py:140-143,
+ * 184-185, 246-253 and datasets/monocular.py:184-187, 222-250 for --hard_sampling).  DESIGN.md section 11. ---- */
+#define NSFF_RAY_RECORD      16   /* floats per training-ray record (monocular.py:180-183): rays_o 0-2, rays_d 3-5, rgb 6-8,
+                                     t 9, disp 10, mask 11, uv_fw 12-13, uv_bw 14-15                                   */
+
+/* The per-pixel, per-channel SSIM LOSS  clamp((1 - ssim) / 2, 0, 1)  of kornia 0.5.4 (11x11 Gaussian window, sigma 1.5,
+ * reflect padding, C1 = 0.01^2, C2 = 0.03^2) of n_frames image pairs; the reference's metric is 1 - loss.  gt / pred: (F, H, W, 3)
+ * fp32, HWC, contiguous.  Outputs (any subset, at least one):
+ *   map       (F, H, W, 3) the loss;
+ *   mean_map  (F, H*W)     its channel mean = the hard-sampling weight 1 - ssim_map.mean(-1) of train.py:253;
+ *   sums      (F, 3) fp64  per frame: sum of the loss over pixels and channels, the same over the pixels with mask != 0,
+ *                          and the number of those pixels (mask (F, H*W) uint8 or NULL = none selected).
+ * sums are combined from per-tile partials in a fixed order (bit-reproducible) in `scratch`: nsff_ssim_scratch_bytes() bytes,
+ * 16-byte aligned, ZERO before its first use (every call leaves it so; one call at a time per scratch buffer).
+ * window must be 11; H, W >= 6 (the reflect padding's minimum) else NSFF_ERR_INVALID. */
+typedef struct NsffSsimArgs {
+    int32_t n_frames, H, W, window;
+    const float* gt;  const float* pred;  const uint8_t* mask;
+    float* map;  float* mean_map;  double* sums;
+    void* scratch;  int64_t scratch_bytes;
+} NsffSsimArgs;
+int64_t nsff_ssim_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int nsff_ssim(const NsffSsimArgs* args, void* stream);
+
+/* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
+int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
+
+/* One training batch of frame `frame` (datasets/monocular.py:233-250) drawn and gathered in one launch: for each b < batch,
+ * idx = first i with cdf[frame][i] > u[b] * cdf[frame][n-1] (cdf non-NULL and that total > 0 and finite), else
+ * floor(u[b] * n_pixels); then the columns of records[frame][idx] go to rays (B,6), rgbs (B,3), ts (B, int64, = (int64) t),
+ * disps (B), rays_mask (B), uv_fw (B,2), uv_bw (B,2); cam_ids (B, int64) zeros and rand_idx (B, int64) = idx where non-NULL.
+ * records (n_frames, n_pixels, NSFF_RAY_RECORD) 16-byte aligned; u (B) in [0, 1). */
+typedef struct NsffRayDrawArgs {
+    int64_t n_frames, n_pixels, frame, batch;
+    const float* records;  const double* cdf;  const float* u;
+    float* rays;  float* rgbs;  int64_t* ts;  int64_t* cam_ids;  float* disps;  float* rays_mask;  float* uv_fw;  float* uv_bw;
+    int64_t* rand_idx;
+} NsffRayDrawArgs;
+int nsff_ray_draw(const NsffRayDrawArgs* args, void* stream);
+
 /* ---- profiling hooks used by bench.py (HIP events around field-query launches) ---- */
 int nsff_prof_enable(int on);
 /* Synchronises the recorded events; returns launches, summed milliseconds and summed

@@ -162,6 +162,21 @@ class FlowGradArgs(C.Structure):
                 ("col_b", C.c_int32), ("pad_", C.c_int32), ("g_a", _fp * 4), ("g_b", _fp * 4), ("out", _fp)]
 
 
+class SsimArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("window", C.c_int32),
+                ("gt", _fp), ("pred", _fp), ("mask", _fp), ("map", _fp), ("mean_map", _fp), ("sums", _fp),
+                ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
+RAY_RECORD = 16
+_DRAW_OUT = ["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
+
+
+class RayDrawArgs(C.Structure):
+    _fields_ = ([("n_frames", C.c_int64), ("n_pixels", C.c_int64), ("frame", C.c_int64), ("batch", C.c_int64),
+                 ("records", _fp), ("cdf", _fp), ("u", _fp)] + [(n, _fp) for n in _DRAW_OUT])
+
+
 # name -> (restype, argtypes); also the list of symbols the header declares
 _SIGNATURES = {
     "nsff_abi_version": (C.c_int, []),
@@ -224,6 +239,10 @@ _SIGNATURES = {
     "nsff_splat_planes": (C.c_int, [C.POINTER(SplatArgs), _fp]),
     "nsff_splat_work_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_mpi_composite": (C.c_int, [C.POINTER(MpiArgs), _fp]),
+    "nsff_ssim_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_ssim": (C.c_int, [C.POINTER(SsimArgs), _fp]),
+    "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
+    "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
     "nsff_prof_collect": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nsff_prof_collect_clock": (C.c_int, [C.POINTER(C.c_int64)] + [C.POINTER(C.c_double)] * 5),
@@ -906,6 +925,72 @@ def mpi_composite(H, W, S, dt, accum_fw, accum_bw, static_rgb, static_alpha, zs,
 
 
 KERNEL_NAMES = {0: None, 1: "f32", 2: "h3_64", 3: "h3_8wave", 4: "h3a", 5: "h3_save", 7: "h3a_tb", 8: "h3a_side", 9: "h3a_save"}
+
+
+def _dptr(t, dtype, what):
+    """Device pointer of a contiguous GPU tensor of `dtype` (None passes through)."""
+    if t is None:
+        return None
+    require_gpu_tensor(t, what)
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"{what}: need a contiguous {dtype} tensor, got {t.dtype}"
+                           f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+    return t.data_ptr()
+
+
+def ssim_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_ssim_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def ssim(gt, pred, mask=None, map=None, mean_map=None, sums=None, scratch=None):
+    """nsff_ssim on (F, H, W, 3) fp32 image pairs: the kornia 0.5.4 SSIM loss map (F, H, W, 3), its channel mean (F, H*W) and
+    the per-frame sums (F, 3) fp64 [loss, masked loss, masked pixels] -- whichever outputs are given.  mask (F, H*W) bool / uint8.
+    scratch: uint8 tensor of ssim_scratch_bytes() bytes, zero before its first use (a fresh zeroed one when None)."""
+    require_gpu_tensor(gt, "ssim: image_gt")
+    require_gpu_tensor(pred, "ssim: image_pred")
+    if gt.dim() != 4 or gt.shape[-1] != 3 or pred.shape != gt.shape:
+        raise RuntimeError(f"ssim: need (F, H, W, 3) image pairs of one shape, got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    F, H, W = (int(v) for v in gt.shape[:3])
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if sums is not None and scratch is None:
+        scratch = torch.zeros(max(ssim_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=gt.device)
+    a = SsimArgs(n_frames=F, H=H, W=W, window=11, gt=_dptr(gt, torch.float32, "ssim: image_gt"),
+                 pred=_dptr(pred, torch.float32, "ssim: image_pred"), mask=_dptr(mask, torch.uint8, "ssim: mask"),
+                 map=_dptr(map, torch.float32, "ssim: map"), mean_map=_dptr(mean_map, torch.float32, "ssim: mean_map"),
+                 sums=_dptr(sums, torch.float64, "ssim: sums"), scratch=_dptr(scratch, torch.uint8, "ssim: scratch"),
+                 scratch_bytes=0 if scratch is None else scratch.numel())
+    for t, n in ((mask, F * H * W), (map, F * H * W * 3), (mean_map, F * H * W), (sums, F * 3)):
+        if t is not None and t.numel() != n:
+            raise RuntimeError(f"ssim: an output / mask has {t.numel()} elements, expected {n}")
+    with torch.cuda.device(gt.device):
+        _check(load().nsff_ssim(C.byref(a), _stream()), "nsff_ssim")
+
+
+def cdf(weights, out):
+    """out (F, N) fp64 = per-frame inclusive prefix sum of weights (F, N) fp32."""
+    F, N = weights.shape
+    if tuple(out.shape) != (F, N):
+        raise RuntimeError("cdf: output shape mismatch")
+    with torch.cuda.device(weights.device):
+        _check(load().nsff_cdf(_dptr(weights, torch.float32, "cdf: weights"), F, N, _dptr(out, torch.float64, "cdf: out"),
+                               _stream()), "nsff_cdf")
+
+
+def ray_draw(records, frame, u, cdf, out):
+    """nsff_ray_draw: records (N_frames, N_pixels, 16) fp32, u (B) fp32 uniforms, cdf (N_frames, N_pixels) fp64 or None
+    (uniform); out: the batch tensors by name (_DRAW_OUT; cam_ids / rand_idx may be absent)."""
+    NF, NP = int(records.shape[0]), int(records.shape[1])
+    if records.dim() != 3 or records.shape[2] != RAY_RECORD:
+        raise RuntimeError(f"ray_draw: records must be (N_frames, N_pixels, {RAY_RECORD})")
+    B = int(u.numel())
+    a = RayDrawArgs(n_frames=NF, n_pixels=NP, frame=int(frame), batch=B, records=_dptr(records, torch.float32, "ray_draw: records"),
+                    cdf=_dptr(cdf, torch.float64, "ray_draw: cdf"), u=_dptr(u, torch.float32, "ray_draw: u"))
+    for n in _DRAW_OUT:
+        t = out.get(n)
+        setattr(a, n, _dptr(t, torch.int64 if n in ("ts", "cam_ids", "rand_idx") else torch.float32, f"ray_draw: {n}"))
+    with torch.cuda.device(records.device):
+        _check(load().nsff_ray_draw(C.byref(a), _stream()), "nsff_ray_draw")
 
 
 def last_field_kernel():

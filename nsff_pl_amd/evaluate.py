@@ -13,6 +13,7 @@ and PSNR -- the renderer-side pieces of the reference's ``eval.py`` / ``datasets
 * :func:`render_frame_sharded` -- the same frame split across the ranks of ``torch.distributed``
                            with one pixel all-gather (:mod:`nsff_pl_amd.dist`).
 * :func:`psnr`          -- metrics.py:6-16.
+* :func:`ssim`          -- metrics.py:19-33 (the reference's SSIM scale, see :mod:`nsff_pl_amd.metrics`).
 """
 import torch
 
@@ -247,3 +248,10 @@ def psnr(image_pred, image_gt, valid_mask=None):
     if valid_mask is not None:
         err = err[valid_mask]
     return -10 * torch.log10(err.mean())
+
+
+def ssim(image_pred, image_gt, valid_mask=None, reduction='mean'):
+    """The reference's SSIM metric (metrics.py:19-33, kornia 0.5.4 window 11) of one (H, W, 3) frame, in this module's
+    (pred, gt) argument order: one HIP launch, see :func:`nsff_pl_amd.metrics.ssim`."""
+    from . import metrics
+    return metrics.ssim(image_gt, image_pred, valid_mask=valid_mask, reduction=reduction)

@@ -8,8 +8,11 @@ ONE flat RCCL all-reduce of the gradients per step instead of DDP's per-bucket h
 2.3 M parameters = 9.2 MB: a single bucket is already far below the xGMI latency/bandwidth knee, so
 splitting it to overlap with backward would only add launches).
 
-Logging, checkpoint callbacks, validation images and hard-sampling buffers of the reference are control
-plane and out of scope.
+Validation reports the reference's ``val_psnr`` and, given the hparam ``img_wh``, ``val_ssim`` (+ ``val_psnr_mask`` /
+``val_ssim_mask`` for a batch with a dynamic ``mask``; train.py:200-243) with the SSIM kernel of :mod:`nsff_pl_amd.metrics`.
+``--hard_sampling`` (train.py:140-143, 184-185, 246-253) is a :class:`nsff_pl_amd.sampling.RayBank` passed as ``ray_bank``:
+the step records ``rgb_fine`` into the bank's ``tmp_rgb`` and validation re-weights the bank's pixels.
+Logging, checkpoint callbacks and validation images of the reference are control plane and out of scope.
 """
 from collections import defaultdict
 
@@ -17,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 from . import field_grad
+from . import metrics
 from .autograd import grad_parameters
 from .losses import NeRFWLoss
 from .optim import FlatAdam
@@ -53,15 +57,21 @@ class NSFFTrainer:
     hparams (attribute or dict access): N_samples, N_importance, perturb, noise_std, chunk, lambda_geo_init,
     thickness, topk, lr, weight_decay, decay_step, decay_gamma -- reference names and defaults (opt.py) -- and
     decay_unused (False: with weight_decay > 0 a parameter that receives no gradient is left alone, as torch.optim.Adam
-    leaves ``grad is None`` parameters alone; True: the plain every-element step, see optim.FlatAdam).
+    leaves ``grad is None`` parameters alone; True: the plain every-element step, see optim.FlatAdam), and img_wh ((W, H) of
+    the validation frames, opt.py's name; None: validation reports val_psnr only).
+
+    ray_bank: a :class:`nsff_pl_amd.sampling.RayBank` the caller draws its batches from.  With ``hard_sampling`` on, every
+    training step records ``rgb_fine`` at the batch's ``(ts, rand_idx)`` and every validation step (or
+    :meth:`update_hard_sampling`) re-weights the bank's pixels by SSIM; checkpoints carry the bank's state.
     """
 
     DEFAULTS = dict(N_samples=128, N_importance=0, perturb=1.0, noise_std=1.0, chunk=32 * 1024,
                     lambda_geo_init=0.04, thickness=1, topk=1.0, lr=5e-4, weight_decay=0.0,
-                    decay_step=[20], decay_gamma=0.1, decay_unused=False)
+                    decay_step=[20], decay_gamma=0.1, decay_unused=False, img_wh=None)
 
     def __init__(self, models, embeddings, n_frames, hparams=None, Ks=None, Ps=None,
-                 output_transient=True, output_transient_flow=("fw", "bw", "disocc"), graph=False, optimizer_cls=FlatAdam):
+                 output_transient=True, output_transient_flow=("fw", "bw", "disocc"), graph=False, optimizer_cls=FlatAdam,
+                 ray_bank=None):
         """graph=True: the step is captured once into two hipGraphs (``torch.cuda.CUDAGraph``) and replayed: graph A =
         zero_grad + forward kernels + loss + backward kernels, graph B = Adam; between them -- outside any capture --
         the flat RCCL gradient all-reduce when world > 1.  Needs fixed batch shapes and topk == 1.
@@ -76,6 +86,7 @@ class NSFFTrainer:
             hp.update({k: v for k, v in given.items() if k in hp})
         self.hp = hp
         self.models, self.embeddings, self.n_frames = models, embeddings, n_frames
+        self.ray_bank = ray_bank
         self.output_transient = output_transient
         self.output_transient_flow = list(output_transient_flow) if output_transient else []
         self._graph_auto = isinstance(graph, str) and graph == "auto"
@@ -173,6 +184,8 @@ class NSFFTrainer:
     def training_step(self, batch):
         kwargs = dict(output_transient=self.output_transient, output_transient_flow=self.output_transient_flow)
         results = self.forward(batch["rays"], batch.get("ts"), **kwargs)
+        if self._hard_sampling():                                        # train.py:184-185
+            self.ray_bank.record(batch, results["rgb_fine"])
         if self.graph:
             kwargs["epoch_ramp"] = self._ramp
         loss_d = self.loss(results, batch, epoch=self.current_epoch, **kwargs)
@@ -184,13 +197,41 @@ class NSFFTrainer:
             log["lr"] = self.optimizer.param_groups[0]["lr"]
         return loss, log
 
-    # train.py:200-214 (the metric part; image grids / SSIM maps of the reference are logging)
+    def _hard_sampling(self):
+        return self.ray_bank is not None and self.ray_bank.hard_sampling
+
+    # train.py:200-253 (the metric part and the hard-sampling update; image grids of the reference are logging)
     @torch.no_grad()
     def validation_step(self, batch):
-        """batch: {'rays': (H*W,6), 'rgbs': (H*W,3) [, 'ts']} of one full frame -> {'val_psnr'}."""
+        """batch: {'rays': (H*W,6), 'rgbs': (H*W,3) [, 'ts'] [, 'mask': (H*W)]} of one full frame -> {'val_psnr'}; with the
+        hparam img_wh also 'val_ssim' (the reference's SSIM of the clipped prediction, train.py:209-219), and with a 'mask'
+        that has static pixels (mask == 0) and output_transient on, 'val_psnr_mask' / 'val_ssim_mask' over those pixels
+        (train.py:240-243).  A hard-sampling ray bank is re-weighted afterwards (train.py:246-253)."""
         kwargs = dict(output_transient=self.output_transient, output_transient_flow=[])
         results = self.forward(batch["rays"], batch.get("ts"), test_time=True, **kwargs)
-        return {"val_psnr": psnr(results["rgb_fine"], batch["rgbs"])}
+        rgb, rgbs = results["rgb_fine"], batch["rgbs"]
+        log = {"val_psnr": psnr(rgb, rgbs)}
+        if self.hp["img_wh"] is not None:
+            W, H = (int(v) for v in self.hp["img_wh"])
+            img = torch.clip(rgb.view(H, W, 3), 0, 1)
+            static = None
+            if self.output_transient and "mask" in batch:
+                static = batch["mask"].reshape(H, W) == 0
+                if not bool(static.any()):
+                    static = None
+            frame, frame_mask = metrics.ssim_maps(rgbs.view(1, H, W, 3), img.unsqueeze(0),
+                                                  None if static is None else static.unsqueeze(0))[1:]
+            log["val_ssim"] = frame[0]
+            if static is not None:
+                log["val_psnr_mask"] = metrics.psnr(rgb, rgbs, static.reshape(-1))
+                log["val_ssim_mask"] = frame_mask[0]
+        if self._hard_sampling():
+            self.update_hard_sampling()
+        return log
+
+    def update_hard_sampling(self):
+        """Re-weight the ray bank's pixels by the SSIM of its recorded predictions (train.py:246-253): two launches."""
+        self.ray_bank.update_weights()
 
     def step(self, batch):
         """zero_grad -> training_step -> backward -> gradient all-reduce -> Adam; returns the log dict."""
@@ -281,7 +322,10 @@ class NSFFTrainer:
         opt = None                                  # (before the first step / to(): no optimizer state exists yet)
         if self.optimizer is not None:
             opt = self.optimizer.torch_state_dict() if hasattr(self.optimizer, "torch_state_dict") else self.optimizer.state_dict()
-        return {"state_dict": sd, "optimizer": opt, "epoch": self.current_epoch}
+        ckpt = {"state_dict": sd, "optimizer": opt, "epoch": self.current_epoch}
+        if self.ray_bank is not None:
+            ckpt["ray_bank"] = self.ray_bank.state_dict()
+        return ckpt
 
     def load_checkpoint(self, ckpt, strict=False, prefixes_to_ignore=()):
         """Inverse of :meth:`checkpoint`; also takes a reference (Lightning) checkpoint: ``state_dict`` with the same
@@ -327,6 +371,8 @@ class NSFFTrainer:
             warnings.warn("load_checkpoint: the checkpoint holds optimizer state but no optimizer exists yet (call .to(device) "
                           "first); Adam moments will start from zero")
         self.current_epoch = int(ckpt.get("epoch", self.current_epoch))
+        if self.ray_bank is not None and "ray_bank" in ckpt:
+            self.ray_bank.load_state_dict(ckpt["ray_bank"])
         self._invalidate_packs()
         return missing
 

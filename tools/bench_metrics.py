@@ -1,0 +1,70 @@
+"""Device-event timings of the SSIM metric and the ray bank (csrc/metrics.hip) at the reference's 512 x 288 frame size.
+
+    python tools/bench_metrics.py                  # JSON line: median microseconds and the HBM byte bound of each case
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_metrics.py --reps 20     # per-kernel times, separately
+
+Cases: one metrics.ssim call (full-frame mean); RayBank.update_weights() over 24 and 100 frames (one SSIM launch writing the
+weights + one fp64 CDF launch); one 1024-ray RayBank.sample() (torch.rand + one draw-and-gather launch).  Byte bounds: the SSIM
+pass reads gt + pred (2 x 12 B per pixel) and writes the 4-B weight per pixel; the CDF reads 4 B and writes 8 B per pixel.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from nsff_pl_amd import metrics  # noqa: E402
+from nsff_pl_amd.sampling import RayBank  # noqa: E402
+
+HBM_PEAK = 8.0e12          # B/s (MI355X datasheet)
+
+
+def time_us(fn, reps, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    times.sort()
+    return times[len(times) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    W, H = 512, 288
+    px = W * H
+    g = torch.Generator(dev).manual_seed(0)
+    out = {"frame": [W, H], "hbm_peak_TBps": HBM_PEAK / 1e12}
+    gt = torch.rand(H, W, 3, device=dev, generator=g)
+    pred = (gt + 0.05 * torch.randn(H, W, 3, device=dev, generator=g)).clamp(0, 1)
+    out["ssim_512x288_us"] = time_us(lambda: metrics.ssim(gt, pred), args.reps)
+    for F in (24, 100):
+        rec = torch.rand(F, px, 16, device=dev, generator=g)
+        bank = RayBank(rec, (W, H), hard_sampling=True, seed=0)
+        bank.tmp_rgb.copy_((bank.rgb + 0.05 * torch.randn(bank.rgb.shape, device=dev, generator=g)).clamp(0, 1))
+        bytes_ = F * px * (24 + 4) + F * px * (4 + 8)
+        t = time_us(bank.update_weights, args.reps)
+        out[f"update_weights_F{F}_us"] = t
+        out[f"update_weights_F{F}_bound_us"] = bytes_ / HBM_PEAK * 1e6
+        if F == 24:
+            out["sample_1024_us"] = time_us(lambda: bank.sample(1024, generator=g), args.reps)
+        del bank, rec
+        torch.cuda.empty_cache()
+    print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
+
+
+if __name__ == "__main__":
+    main()
