@@ -745,6 +745,19 @@ int         nsff_last_field_grid(void);
 int         nsff_field_phase_program(const NsffModelDesc* desc, int static_mode, int transient_mode, int fold_t, uint32_t* steps,
                              int* n_steps, int* n_static_steps, uint32_t* phases_static, uint32_t* phases_dynamic, int* n_phases);
 
+/* ---- f16x3 value-domain flag ----
+ * The f16x3 kernels carry every fp32 operand as hi + lo halfs with hi = rtz_f16(x): exact to fp32 rounding only while
+ * |x| <= 65504.  Every kernel that splits an fp32 value into fp16 MFMA operands ORs one bit per source into a sticky 32-bit
+ * word of the current device when a value with !(|x| <= 65504) reached the split (inf included; NaN where the check sees it --
+ * a ReLU or a max drops it).  Values are never changed: the flag only records.  The "f32" kernels never set a bit. */
+#define NSFF_RANGE_ACT     0x1u   /* trunk activations / position input rows of an f16x3 inference launch          */
+#define NSFF_RANGE_SAVED   0x2u   /* activations and input rows of the training forward (the fp16 tiles it saves)     */
+#define NSFF_RANGE_PARAMS  0x4u   /* parameters at packing time (nsff_pack_weights f16x3, nsff_pack_weights_bwd)      */
+#define NSFF_RANGE_CODES   0x8u   /* time / appearance / view-direction code columns of an f16x3 input tile           */
+/* Asynchronous on `stream` (graph-capturable): one tiny kernel copies the current device's word to the DEVICE pointer `out`
+ * and, clear != 0, zeroes it (atomically: a bit set concurrently is either reported or kept). */
+int         nsff_range_flags(uint32_t* out, int32_t clear, void* stream);
+
 int         nsff_abi_version(void);
 const char* nsff_last_hip_error(void);
 

@@ -7,9 +7,11 @@ Public surface = the reference's own interface for that path:
 All arithmetic runs in the gfx950 kernels of ``csrc/`` behind the C-ABI declared in
 ``include/nsff_render.h``; see DESIGN.md / INTEGRATION.md.
 """
-from .config import get_precision, set_precision
+from .config import get_precision, set_precision, get_range_check, set_range_check
+from .range_check import RangeFlags, range_flags
 from .nerf import NeRF, PosEmbedding
 from .rendering import render_rays, sample_pdf
 from .interpolation import interpolate
 
-__all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "set_precision", "get_precision"]
+__all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "set_precision", "get_precision",
+           "set_range_check", "get_range_check", "range_flags", "RangeFlags"]

@@ -180,6 +180,7 @@ class RayDrawArgs(C.Structure):
 # name -> (restype, argtypes); also the list of symbols the header declares
 _SIGNATURES = {
     "nsff_abi_version": (C.c_int, []),
+    "nsff_range_flags": (C.c_int, [_fp, C.c_int32, _fp]),
     "nsff_last_field_kernel": (C.c_int, []),
     "nsff_last_field_grid": (C.c_int, []),
     "nsff_field_phase_program": (C.c_int, [C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int),
@@ -991,6 +992,12 @@ def ray_draw(records, frame, u, cdf, out):
         setattr(a, n, _dptr(t, torch.int64 if n in ("ts", "cam_ids", "rand_idx") else torch.float32, f"ray_draw: {n}"))
     with torch.cuda.device(records.device):
         _check(load().nsff_ray_draw(C.byref(a), _stream()), "nsff_ray_draw")
+
+
+def range_flags(out, clear):
+    """nsff_range_flags: the current device's value-domain word -> out (a 1-element int32 GPU tensor), cleared when `clear`"""
+    assert out.is_cuda and out.dtype == torch.int32 and out.numel() >= 1
+    _check(load().nsff_range_flags(out.data_ptr(), 1 if clear else 0, _stream()), "nsff_range_flags")
 
 
 def last_field_kernel():

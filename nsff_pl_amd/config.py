@@ -6,6 +6,19 @@ precision
                ~2.7x faster.
     "f32"   -- exact fp32 MFMA (v_mfma_f32_32x32x2_f32).
 Select with ``set_precision`` or the environment variable ``NSFF_PRECISION``.
+
+range check (the value domain of "f16x3")
+    "f16x3" carries an operand x as hi + lo halfs with hi = rtz_f16(x): fp32-grade only while |x| <= 65504.  Every kernel
+    that splits fp32 values into fp16 MFMA operands records, in a sticky per-device word, whether any such value fell outside
+    that range (one bit per source: :class:`nsff_pl_amd.range_check.RangeFlags`); the values themselves never change.
+    ``nsff_pl_amd.range_flags()`` reads (and clears) the word -- one tiny launch and a sync, e.g. once per frame or epoch.
+    ``set_range_check(mode)`` / ``NSFF_RANGE_CHECK`` makes the Python layer check around every call instead:
+    "off"      -- (default) nothing is read: no extra launch or sync;
+    "warn"     -- ``render_rays``, ``NeRF.forward`` and ``NSFFTrainer.step`` clear the word before the call and read it after
+                  (two tiny launches and a sync per call) and issue a RuntimeWarning naming the sources;
+    "raise"    -- the same check, raising RuntimeError (the trainer raises before Adam: weights and optimizer state untouched);
+    "fallback" -- deterministic inference calls (``NeRF.forward``; ``render_rays(test_time=True)`` with perturb == 0 and
+                  noise_std == 0) that were flagged run again in "f32" and return that result; other calls behave as "raise".
 """
 import os
 
@@ -120,3 +133,22 @@ class launch_form:
         global _persistent
         _persistent = self.old
         return False
+
+
+RANGE_CHECKS = ("off", "warn", "raise", "fallback")
+_range_check = os.environ.get("NSFF_RANGE_CHECK", "off")
+if _range_check not in RANGE_CHECKS:
+    raise RuntimeError(f"NSFF_RANGE_CHECK must be one of {list(RANGE_CHECKS)}")
+
+
+def set_range_check(mode):
+    """What the Python layer does about f16x3 operands outside the fp16 range: "off", "warn", "raise" or "fallback"
+    (see the module docstring)."""
+    global _range_check
+    if mode not in RANGE_CHECKS:
+        raise ValueError(f"range check must be one of {list(RANGE_CHECKS)}")
+    _range_check = mode
+
+
+def get_range_check():
+    return _range_check

@@ -416,10 +416,45 @@ double field_flops_per_point(const NsffModelDesc& d, int static_mode, int transi
 
 }  // namespace
 
+// The f16x3 value-domain word of each device (NSFF_RANGE_*): zero at module load, set by the f16x3 kernels, read and cleared
+// only by nsff_range_flags.  Its address is resolved per device on the first call outside a stream capture (nsff_range_flags,
+// and every launch that needs it) -- resolving it may load the module, which a capture must not see.
+__device__ uint32_t g_nsff_range_word;
+
+uint32_t* nsff_range_word(hipStream_t st) {
+    static uint32_t* addr[64];
+    static std::mutex lock;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    std::lock_guard<std::mutex> guard(lock);
+    if (addr[dev] == nullptr) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_nsff_range_word)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        addr[dev] = static_cast<uint32_t*>(p);
+    }
+    return addr[dev];
+}
+
+namespace {
+__global__ void nsff_range_flags_kernel(uint32_t* out, int clear) {
+    if (threadIdx.x == 0) *out = clear ? atomicExch(&g_nsff_range_word, 0u) : atomicOr(&g_nsff_range_word, 0u);
+}
+}  // namespace
+
 extern "C" {
 
 int nsff_abi_version(void) { return NSFF_ABI_VERSION; }
 const char* nsff_last_hip_error(void) { return hipGetErrorString(g_nsff_last_err); }
+
+int nsff_range_flags(uint32_t* out, int32_t clear, void* stream) {
+    if (!out) return NSFF_ERR_NULL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    (void)nsff_range_word(st);              // (outside a capture: resolves the address for the kernels' later launches)
+    hipLaunchKernelGGL(nsff_range_flags_kernel, dim3(1), dim3(64), 0, st, out, clear ? 1 : 0);
+    return nsff_launch_status();
+}
 
 int nsff_packed_bytes(const NsffModelDesc* desc, int precision, size_t* bytes) {
     if (!desc || !bytes) return NSFF_ERR_NULL;

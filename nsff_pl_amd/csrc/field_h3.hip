@@ -118,6 +118,7 @@ struct H3KArgs {
     float freqs[NSFF_MAX_FREQS];
     int ld_emb, off_xyz, off_dir, off_a, off_t;
     unsigned long long* span;        // profiling only (else null): per-XCD first / last s_memtime tick of the launch
+    uint32_t* range;                 // the device's value-domain word (nsff_range_word), or null
 };
 
 // Shader clock under load (profiling only, span != null): every 16th workgroup measures its own lifetime in shader-clock ticks
@@ -144,7 +145,9 @@ __device__ __forceinline__ void span_end(unsigned long long* span, const SpanT& 
 #define MFMA_H(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 #define H3_PIN() __builtin_amdgcn_sched_barrier(0)
 
-__device__ __forceinline__ void split_store(_Float16* xh, _Float16* xl, int idx, float v) {
+// (every split below also folds |v| into the caller's running max `rm`: the value-domain check, NSFF_RANGE_*)
+__device__ __forceinline__ void split_store(_Float16* xh, _Float16* xl, int idx, float v, float& rm) {
+    rm = nsff_absmax3(rm, v, v);
     const _Float16 hi = (_Float16)v;
     xh[idx] = hi;
     xl[idx] = (_Float16)(v - (float)hi);
@@ -362,8 +365,9 @@ __device__ __forceinline__ unsigned positive_flag(float v) {
 // rowh / rowl: this lane's point row at the tile's first neuron.  MASKS: also collect the ReLU sign bits, bit 4q + e of
 // `signs` (+ sign_shift) -- 2 VALU per value.
 template <bool RELU, bool MASKS>
+// rm: the lane's running max of |value| (value-domain check: two v_max3 per four values)
 __device__ __forceinline__ void acc_store_unit(_Float16* rowh, _Float16* rowl, const f32x16& t, int p, int lane,
-                                               unsigned& signs, int sign_shift) {
+                                               unsigned& signs, int sign_shift, float& rm) {
     h4 hq[2], lq[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -375,6 +379,7 @@ __device__ __forceinline__ void acc_store_unit(_Float16* rowh, _Float16* rowl, c
             if (RELU) v[e] = relu1(v[e]);
             if constexpr (MASKS) signs |= positive_flag(v[e]) << (sign_shift + 4 * q + e);
         }
+        rm = nsff_absmax3(nsff_absmax3(rm, v[0], v[1]), v[2], v[3]);
         const h2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]);
         const h2 h23 = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
         const h2 l01 = __builtin_amdgcn_cvt_pkrtz(minus_lo_half(h01, v[0]), minus_hi_half(h01, v[1]));
@@ -392,7 +397,7 @@ __device__ __forceinline__ void acc_store_unit(_Float16* rowh, _Float16* rowl, c
 // kernel (64-point tiles, four waves of 64 neurons x [mt][nt]) reads word [tile][64 w + lane], bit ((mt * 2 + nt) * 4 + q) * 4 + e.
 template <int NT, bool RELU, int MTW, bool MASKS = false>
 __device__ __forceinline__ void acc_store(_Float16* sXh, _Float16* sXl, const f32x16 (&acc)[MTW][NT], int nb0, int nt0, int lane,
-                                          unsigned long long* mask = nullptr, bool two_tiles = true) {
+                                          float& rm, unsigned long long* mask = nullptr, bool two_tiles = true) {
     unsigned signs[2] = {0u, 0u};                  // two tiles of 16 values per 32-bit word
 #pragma unroll
     for (int mt = 0; mt < MTW; ++mt)
@@ -402,7 +407,7 @@ __device__ __forceinline__ void acc_store(_Float16* sXh, _Float16* sXl, const f3
             const int ti = mt * NT + nt;
 #pragma unroll
             for (int p = 0; p < 2; ++p)
-                acc_store_unit<RELU, MASKS>(sXh + row, sXl + row, acc[mt][nt], p, lane, signs[ti >> 1], 16 * (ti & 1));
+                acc_store_unit<RELU, MASKS>(sXh + row, sXl + row, acc[mt][nt], p, lane, signs[ti >> 1], 16 * (ti & 1), rm);
         }
     if constexpr (MASKS) {
         unsigned* m32 = reinterpret_cast<unsigned*>(mask);
@@ -477,7 +482,8 @@ __device__ __forceinline__ void tile_to_fragments(const _Float16* sXh, const _Fl
 }
 
 // four consecutive columns of one row -> one 8-byte store per plane
-__device__ __forceinline__ void split_store4(_Float16* xh, _Float16* xl, int idx, const float4 v) {
+__device__ __forceinline__ void split_store4(_Float16* xh, _Float16* xl, int idx, const float4 v, float& rm) {
+    rm = nsff_absmax3(nsff_absmax3(rm, v.x, v.y), v.z, v.w);
     h4 hv, lv;
     hv[0] = (_Float16)v.x; hv[1] = (_Float16)v.y; hv[2] = (_Float16)v.z; hv[3] = (_Float16)v.w;
     *reinterpret_cast<h4*>(xh + idx) = hv;
@@ -506,7 +512,8 @@ __device__ __forceinline__ int build_part(int tid) {
 }
 
 // two consecutive columns (idx even) -> one 4-byte store per plane
-__device__ __forceinline__ void split_store2(_Float16* xh, _Float16* xl, int idx, float v0, float v1) {
+__device__ __forceinline__ void split_store2(_Float16* xh, _Float16* xl, int idx, float v0, float v1, float& rm) {
+    rm = nsff_absmax3(rm, v0, v1);
     const h2 h = __builtin_amdgcn_cvt_pkrtz(v0, v1);
     *reinterpret_cast<h2*>(xh + idx) = h;
     *reinterpret_cast<h2*>(xl + idx) = __builtin_amdgcn_cvt_pkrtz(minus_lo_half(h, v0), minus_hi_half(h, v1));
@@ -540,7 +547,7 @@ __device__ __forceinline__ void sincos_cw(float a, float* s, float* c) {
 // call, one reduction at a time, for their register budget
 template <int M, int THREADS, bool OCTAVE = true, bool ILP = false, class KA = H3KArgs>
 __device__ __forceinline__ void build_input(_Float16* sXh, _Float16* sXl, const KA& a, long long p0, bool with_t,
-                                            const float (&x)[3], int tid) {
+                                            const float (&x)[3], int tid, float& rm, float& rmc) {
     constexpr int G = THREADS / M;               // threads per point row
     constexpr int CH = 16 / G;                   // float4 chunks of a 64-column time-code segment per thread
     const int r = build_row<M, THREADS>(tid), q = build_part<M, THREADS>(tid);
@@ -586,10 +593,10 @@ __device__ __forceinline__ void build_input(_Float16* sXh, _Float16* sXl, const 
         for (int k = 0; k < OPP; ++k) {
             if (f0 + k >= a.n_freqs) { sn[0] = sn[1] = sn[2] = cs[0] = cs[1] = cs[2] = 0.f; }   // (zero padding up to k0s)
             const int ck = c0 + 6 * k;                              // [sin x3 | cos x3] of octave f0 + k
-            if (k == 0) split_store(sXh, sXl, base + ck, sn[0]);
-            else if (ck - 1 < k0s) split_store2(sXh, sXl, base + ck - 1, carry, sn[0]);
-            if (ck + 1 < k0s) split_store2(sXh, sXl, base + ck + 1, sn[1], sn[2]);
-            if (ck + 3 < k0s) split_store2(sXh, sXl, base + ck + 3, cs[0], cs[1]);
+            if (k == 0) split_store(sXh, sXl, base + ck, sn[0], rm);
+            else if (ck - 1 < k0s) split_store2(sXh, sXl, base + ck - 1, carry, sn[0], rm);
+            if (ck + 1 < k0s) split_store2(sXh, sXl, base + ck + 1, sn[1], sn[2], rm);
+            if (ck + 3 < k0s) split_store2(sXh, sXl, base + ck + 3, cs[0], cs[1], rm);
             carry = cs[2];
             if (k + 1 < OPP) {
                 if (k == 2 && f0 + 3 < a.n_freqs) {        // (five octaves per part only)
@@ -607,34 +614,34 @@ __device__ __forceinline__ void build_input(_Float16* sXh, _Float16* sXl, const 
                 }
             }
         }
-        if (c0 + 6 * OPP - 1 < k0s) split_store(sXh, sXl, base + c0 + 6 * OPP - 1, carry);
+        if (c0 + 6 * OPP - 1 < k0s) split_store(sXh, sXl, base + c0 + 6 * OPP - 1, carry, rm);
         if (q == G - 1)                                             // columns past the last part's range (G = 2: column 63)
-            for (int c = 3 + 6 * OPP * G; c < k0s; ++c) split_store(sXh, sXl, base + c, 0.f);
+            for (int c = 3 + 6 * OPP * G; c < k0s; ++c) split_store(sXh, sXl, base + c, 0.f, rm);
         if (q == 0) {
-            split_store2(sXh, sXl, base + 0, x[0], x[1]);
-            split_store(sXh, sXl, base + 2, x[2]);
+            split_store2(sXh, sXl, base + 0, x[0], x[1], rm);
+            split_store(sXh, sXl, base + 2, x[2], rm);
         }
     } else if (a.xyz != nullptr) {
         if (q == 0) {
-            split_store(sXh, sXl, base + 0, x[0]); split_store(sXh, sXl, base + 1, x[1]);
-            split_store(sXh, sXl, base + 2, x[2]);
-            for (int c = a.in_xyz; c < k0s; ++c) split_store(sXh, sXl, base + c, 0.f);
+            split_store(sXh, sXl, base + 0, x[0], rm); split_store(sXh, sXl, base + 1, x[1], rm);
+            split_store(sXh, sXl, base + 2, x[2], rm);
+            for (int c = a.in_xyz; c < k0s; ++c) split_store(sXh, sXl, base + c, 0.f, rm);
         }
         const int nf3 = 3 * a.n_freqs;
         for (int j = q; j < nf3; j += G) {
             const int f = j / 3, c = j - 3 * f;
             float s, co;
             sincosf(a.freqs[f] * x[c], &s, &co);
-            split_store(sXh, sXl, base + 3 + 6 * f + c, s);
-            split_store(sXh, sXl, base + 3 + 6 * f + 3 + c, co);
+            split_store(sXh, sXl, base + 3 + 6 * f + c, s, rm);
+            split_store(sXh, sXl, base + 3 + 6 * f + 3 + c, co, rm);
         }
     } else {
         const float* src = a.x_emb + p * a.ld_emb + a.off_xyz;
-        for (int c = q; c < k0s; c += G) split_store(sXh, sXl, base + c, (valid && c < a.in_xyz) ? src[c] : 0.f);
+        for (int c = q; c < k0s; c += G) split_store(sXh, sXl, base + c, (valid && c < a.in_xyz) ? src[c] : 0.f, rm);
     }
     if (vec_t) {
 #pragma unroll
-        for (int j = 0; j < CH0; ++j) split_store4(sXh, sXl, base + k0s + 4 * (q + j * G), tv[j]);
+        for (int j = 0; j < CH0; ++j) split_store4(sXh, sXl, base + k0s + 4 * (q + j * G), tv[j], rmc);
         if constexpr (CH > CH0) {                     // two threads per row: the second half of the 16 chunks
 #pragma unroll
             for (int j = CH0; j < CH; ++j) {
@@ -642,17 +649,17 @@ __device__ __forceinline__ void build_input(_Float16* sXh, _Float16* sXl, const 
                 tv[j - CH0] = (valid && c < a.in_t) ? *reinterpret_cast<const float4*>(tsrc + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
-            for (int j = CH0; j < CH; ++j) split_store4(sXh, sXl, base + k0s + 4 * (q + j * G), tv[j - CH0]);
+            for (int j = CH0; j < CH; ++j) split_store4(sXh, sXl, base + k0s + 4 * (q + j * G), tv[j - CH0], rmc);
         }
     } else if (with_t) {
         for (int c = q; c < kt; c += G)
-            split_store(sXh, sXl, base + k0s + c, (valid && c < a.in_t) ? tsrc[c] : 0.f);
+            split_store(sXh, sXl, base + k0s + c, (valid && c < a.in_t) ? tsrc[c] : 0.f, rmc);
     }
 }
 
 // the time-code columns [k0s, k0s + kt) of the trunk input tile alone (the position part is someone else's): float4 rows
 template <int M, int THREADS, class KA = H3KArgs>
-__device__ __forceinline__ void build_time_part(_Float16* sXh, _Float16* sXl, const KA& a, long long p0, int tid) {
+__device__ __forceinline__ void build_time_part(_Float16* sXh, _Float16* sXl, const KA& a, long long p0, int tid, float& rmc) {
     constexpr int G = THREADS / M;
     constexpr int CH = 16 / G;
     const int r = build_row<M, THREADS>(tid), q = build_part<M, THREADS>(tid);
@@ -667,11 +674,11 @@ __device__ __forceinline__ void build_time_part(_Float16* sXh, _Float16* sXl, co
         tv[j] = (valid && c < a.in_t) ? *reinterpret_cast<const float4*>(tsrc + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
-    for (int j = 0; j < CH; ++j) split_store4(sXh, sXl, r * LDH + k0s + 4 * (q + j * G), tv[j]);
+    for (int j = 0; j < CH; ++j) split_store4(sXh, sXl, r * LDH + k0s + 4 * (q + j * G), tv[j], rmc);
 }
 
 template <int M, int THREADS>
-__device__ __forceinline__ void build_side(_Float16* sXh, _Float16* sXl, const H3KArgs& a, long long p0, int tid) {
+__device__ __forceinline__ void build_side(_Float16* sXh, _Float16* sXl, const H3KArgs& a, long long p0, int tid, float& rmc) {
     constexpr int G = THREADS / M;
     const int r = build_row<M, THREADS>(tid), q = build_part<M, THREADS>(tid);
     const long long p = p0 + r;
@@ -694,7 +701,7 @@ __device__ __forceinline__ void build_side(_Float16* sXh, _Float16* sXl, const H
             if (c < a.in_dir) v = sd[c];
             else if (c < a.in_dir + a.in_a) v = sa[c - a.in_dir];
         }
-        split_store(sXh, sXl, r * LDH + c, v);
+        split_store(sXh, sXl, r * LDH + c, v, rmc);
     }
 }
 
@@ -917,6 +924,7 @@ __global__ __launch_bounds__(256 * WM * (3 - MTW), (NT == 2 ? 2 : 1)) void nsff_
     };
     H3_SPAN(0);
     const SpanT span0 = span_begin(a.span);
+    float rm = 0.f, rmc = 0.f;                     // running max of |value| over this lane's splits: activations + positions, codes
     const H3Step s0 = step_at(s_begin);
     const uint4* wnext = prefetch_w<MTW>(ring, seg(s0.w_off, s0.nks));
     load_bias<MTW>(br, fbias(s0.bias_off), nb0, lane);
@@ -928,10 +936,10 @@ __global__ __launch_bounds__(256 * WM * (3 - MTW), (NT == 2 ? 2 : 1)) void nsff_
             pend_flush();                          // (a tile nobody multiplied after it was saved: the last one of a trunk)
             __syncthreads();                       // everyone is done reading the previous tile
             if (st.pre == PRE_SIDE) {
-                build_side<M, THREADS>(sXh, sXl, a, p0, threadIdx.x);
+                build_side<M, THREADS>(sXh, sXl, a, p0, threadIdx.x, rmc);
             } else {
                 if constexpr (!KEEP_POINT) read_point();
-                build_input<M, THREADS, !SAVE>(sXh, sXl, a, p0, st.pre == PRE_INPUT_T, px, threadIdx.x);
+                build_input<M, THREADS, !SAVE>(sXh, sXl, a, p0, st.pre == PRE_INPUT_T, px, threadIdx.x, rm, rmc);
             }
             __syncthreads();
             if constexpr (SAVE) {
@@ -1000,9 +1008,9 @@ __global__ __launch_bounds__(256 * WM * (3 - MTW), (NT == 2 ? 2 : 1)) void nsff_
                     mk = a.save_masks + ((long long)(st.save - 1) * a.n_tiles + tile64) * 256;   // (per-thread slot: acc_store)
             }
             if (st.post == POST_RELU) {
-                if (SAVE && mk != nullptr) acc_store<NT, true, MTW, SAVE>(sXh, sXl, acc, nb0, nt0, lane, mk, ks_end > 4);
-                else acc_store<NT, true, MTW>(sXh, sXl, acc, nb0, nt0, lane);
-            } else acc_store<NT, false, MTW>(sXh, sXl, acc, nb0, nt0, lane);
+                if (SAVE && mk != nullptr) acc_store<NT, true, MTW, SAVE>(sXh, sXl, acc, nb0, nt0, lane, rm, mk, ks_end > 4);
+                else acc_store<NT, true, MTW>(sXh, sXl, acc, nb0, nt0, lane, rm);
+            } else acc_store<NT, false, MTW>(sXh, sXl, acc, nb0, nt0, lane, rm);
             H3_STAMP(4);
             __syncthreads();
             H3_STAMP(5);
@@ -1020,6 +1028,8 @@ __global__ __launch_bounds__(256 * WM * (3 - MTW), (NT == 2 ? 2 : 1)) void nsff_
         }
     }
     pend_flush();
+    nsff_range_flag(a.range, rm, SAVE ? NSFF_RANGE_SAVED : NSFF_RANGE_ACT, lane);
+    nsff_range_flag(a.range, rmc, NSFF_RANGE_CODES, lane);
     { [[maybe_unused]] const int wave = wave_id; H3_HSTAMP(4); }
     __syncthreads();
     { [[maybe_unused]] const int wave = wave_id; H3_HSTAMP(5); }
@@ -1129,16 +1139,17 @@ struct H3APre {
 // of the three axes -- a sincos at its first and fourth octave, the others by angle doubling (as build_input's OCTAVE path) --
 // and stores its 33 / 31 columns as 16-byte LDS stores per plane: q = 0 columns 0..31 and column 32, q = 1 column 33, 34..35,
 // 36..39, 40..63 (column 63 = 0).  Rows of points past the end are encoded like any other (their records are never stored).
-__device__ __forceinline__ void h3a_split2(float v0, float v1, unsigned& h, unsigned& l) {
+__device__ __forceinline__ void h3a_split2(float v0, float v1, unsigned& h, unsigned& l, float& rm) {
+    rm = nsff_absmax3(rm, v0, v1);
     const h2 hh = __builtin_amdgcn_cvt_pkrtz(v0, v1);
     const h2 ll = __builtin_amdgcn_cvt_pkrtz(minus_lo_half(hh, v0), minus_hi_half(hh, v1));
     h = __builtin_bit_cast(unsigned, hh);
     l = __builtin_bit_cast(unsigned, ll);
 }
-__device__ __forceinline__ void h3a_store8(_Float16* rh, _Float16* rl, int col, const float* w) {
+__device__ __forceinline__ void h3a_store8(_Float16* rh, _Float16* rl, int col, const float* w, float& rm) {
     unsigned h[4], l[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) h3a_split2(w[2 * i], w[2 * i + 1], h[i], l[i]);
+    for (int i = 0; i < 4; ++i) h3a_split2(w[2 * i], w[2 * i + 1], h[i], l[i], rm);
     *reinterpret_cast<u4v*>(rh + col) = u4v{h[0], h[1], h[2], h[3]};
     *reinterpret_cast<u4v*>(rl + col) = u4v{l[0], l[1], l[2], l[3]};
 }
@@ -1151,7 +1162,8 @@ __device__ __forceinline__ void h3a_store8(_Float16* rh, _Float16* rl, int col, 
 // class of the library call at a third of its instructions), because the gradients are compared with autograd of the reference
 // network, whose ReLU pattern answers a 4-ulp change of the encoding with per-cent changes of single weight gradients.
 template <bool EXACT, class Pre, class KA = H3KArgs>
-__device__ __forceinline__ void h3a_encode10(_Float16* sXh, _Float16* sXl, const KA& a, const float (&x)[3], int tid, const Pre& pre) {
+__device__ __forceinline__ void h3a_encode10(_Float16* sXh, _Float16* sXl, const KA& a, const float (&x)[3], int tid, const Pre& pre,
+                                             float& rm) {
     const int r = tid & 127;
     const int q = __builtin_amdgcn_readfirstlane(tid >> 7);
     const float fa = a.freqs[5 * q], fb = a.freqs[5 * q + 3];
@@ -1190,24 +1202,24 @@ __device__ __forceinline__ void h3a_encode10(_Float16* sXh, _Float16* sXl, const
         w[0] = x[0]; w[1] = x[1]; w[2] = x[2];
 #pragma unroll
         for (int i = 0; i < 29; ++i) w[3 + i] = v[i];
-        h3a_store8(rh, rl, 0, w);
+        h3a_store8(rh, rl, 0, w, rm);
         pre.template slot<6>();
-        h3a_store8(rh, rl, 8, w + 8);
-        h3a_store8(rh, rl, 16, w + 16);
+        h3a_store8(rh, rl, 8, w + 8, rm);
+        h3a_store8(rh, rl, 16, w + 16, rm);
         pre.template slot<7>();
-        h3a_store8(rh, rl, 24, w + 24);
-        h3a_split2(v[29], 0.f, h, l);
+        h3a_store8(rh, rl, 24, w + 24, rm);
+        h3a_split2(v[29], 0.f, h, l, rm);
         *reinterpret_cast<unsigned short*>(rh + 32) = (unsigned short)h;
         *reinterpret_cast<unsigned short*>(rl + 32) = (unsigned short)l;
     } else {
-        h3a_split2(v[0], 0.f, h, l);
+        h3a_split2(v[0], 0.f, h, l, rm);
         *reinterpret_cast<unsigned short*>(rh + 33) = (unsigned short)h;
         *reinterpret_cast<unsigned short*>(rl + 33) = (unsigned short)l;
-        h3a_split2(v[1], v[2], h, l);
+        h3a_split2(v[1], v[2], h, l, rm);
         *reinterpret_cast<unsigned*>(rh + 34) = h;
         *reinterpret_cast<unsigned*>(rl + 34) = l;
         unsigned hb, lb;
-        h3a_split2(v[3], v[4], h, l); h3a_split2(v[5], v[6], hb, lb);
+        h3a_split2(v[3], v[4], h, l, rm); h3a_split2(v[5], v[6], hb, lb, rm);
         *reinterpret_cast<u2v*>(rh + 36) = u2v{h, hb};
         *reinterpret_cast<u2v*>(rl + 36) = u2v{l, lb};
         pre.template slot<6>();
@@ -1215,10 +1227,10 @@ __device__ __forceinline__ void h3a_encode10(_Float16* sXh, _Float16* sXl, const
 #pragma unroll
         for (int i = 0; i < 23; ++i) w[i] = v[7 + i];
         w[23] = 0.f;
-        h3a_store8(rh, rl, 40, w);
+        h3a_store8(rh, rl, 40, w, rm);
         pre.template slot<7>();
-        h3a_store8(rh, rl, 48, w + 8);
-        h3a_store8(rh, rl, 56, w + 16);
+        h3a_store8(rh, rl, 48, w + 8, rm);
+        h3a_store8(rh, rl, 56, w + 16, rm);
     }
 }
 
@@ -1420,13 +1432,18 @@ __device__ __forceinline__ void h3a_kernel() {
     // (the lean encoder builds the position part; the dynamic trunk's time-code columns -- when they go through the matrix pipe:
     //  no folded rows, and every training forward -- are appended by build_time_part)
     const bool lean = a.octave_freqs && a.n_freqs == 10 && (SAVE || !(tr == 1 && !tb));
+    // value-domain check (NSFF_RANGE_*): the encoder's maximum |x| of this lane's position columns enters the body (%[rm0]), which
+    // adds its epilogues' and issues the tile's one atomic; the time-code columns are flagged here (the body's skip-layer rebuild
+    // splits the same values again)
+    float rm = 0.f, rmc = 0.f;
     if (lean) {
-        h3a_encode10<SAVE>(sXh, sXl, a, px, tid_, pre);
-        if (SAVE && tr == 1 && !tb) build_time_part<M, THREADS>(sXh, sXl, a, p0, tid_);
+        h3a_encode10<SAVE>(sXh, sXl, a, px, tid_, pre, rm);
+        if (SAVE && tr == 1 && !tb) build_time_part<M, THREADS>(sXh, sXl, a, p0, tid_, rmc);
     } else {
         pre.slot<3>(); pre.slot<4>(); pre.slot<5>(); pre.slot<6>(); pre.slot<7>();
-        build_input<M, THREADS, !SAVE, true>(sXh, sXl, a, p0, tr == 1 && !tb, px, tid_);
+        build_input<M, THREADS, !SAVE, true>(sXh, sXl, a, p0, tr == 1 && !tb, px, tid_, rm, rmc);
     }
+    if (tr == 1 && !tb) nsff_range_flag(a.range, rmc, NSFF_RANGE_CODES, (unsigned)lane);
     // the bias rows go to LDS behind the encoder (a later tile's per-ray rows were requested in front of it), then the NEXT tile's
     // point is requested: it lands under the body
     if (it == 0) {
@@ -1490,6 +1507,7 @@ __device__ __forceinline__ void h3a_kernel() {
         const unsigned in_t = (tr == 1 && !tb) ? (unsigned)a.in_t : 0u;
         const unsigned tpa0 = (unsigned)((uintptr_t)tpa), tpa1 = (unsigned)((uintptr_t)tpa >> 32);
         const unsigned tpb0 = (unsigned)((uintptr_t)tpb), tpb1 = (unsigned)((uintptr_t)tpb >> 32);
+        const unsigned long long rflag = (unsigned long long)(uintptr_t)a.range;
 #ifdef H3_TIMING
         // 256 dwords per (workgroup & 255, wave): [0] kernel entry, [1] input built, [52..] C++ stamps, [62] body left, [63] records
         // stored, [64 + 6 i ..] the body's records: dispatcher visit i and the five stamps of the phase before it
@@ -1502,7 +1520,8 @@ __device__ __forceinline__ void h3a_kernel() {
                          : [tid] "+v"(tid_)
                          : [pk] "s"(pkb), [phases] "s"(phases), [lds] "s"(lds), [biaslds] "s"(biaslds), [rawlds] "s"((unsigned)(uintptr_t)sRaw),
                            [wave] "s"(wave_id), [in_t] "s"(in_t), [tpa0] "v"(tpa0), [tpa1] "v"(tpa1), [tpb0] "v"(tpb0), [tpb1] "v"(tpb1),
-                           [act] "s"(sv_act), [mask] "s"(sv_mask), [astride] "s"(sv_astride), [mstride] "s"(sv_mstride)
+                           [act] "s"(sv_act), [mask] "s"(sv_mask), [astride] "s"(sv_astride), [mstride] "s"(sv_mstride),
+                           [rflag] "s"(rflag), [rm0] "v"(rm)
                          : H3A_SAVE_CLOBBERS);
         } else {
         asm volatile(H3A_BODY
@@ -1512,7 +1531,8 @@ __device__ __forceinline__ void h3a_kernel() {
                        [dbg] "s"(dbg),
 #endif
                        [phases] "s"(phases), [lds] "s"(lds), [biaslds] "s"(biaslds), [rawlds] "s"((unsigned)(uintptr_t)sRaw),
-                       [wave] "s"(wave_id), [in_t] "s"(in_t), [tpa0] "v"(tpa0), [tpa1] "v"(tpa1), [tpb0] "v"(tpb0), [tpb1] "v"(tpb1)
+                       [wave] "s"(wave_id), [in_t] "s"(in_t), [tpa0] "v"(tpa0), [tpa1] "v"(tpa1), [tpb0] "v"(tpb0), [tpb1] "v"(tpb1),
+                       [rflag] "s"(rflag), [rm0] "v"(rm)
                      : H3A_CLOBBERS);
         }
     }
@@ -1741,7 +1761,7 @@ struct PackSegH3 {
     int32_t row0, nrows;          // head: destination row range
 };
 constexpr int PACK_BATCH = 56;          // one launch per model (3.1 KB of kernel arguments)
-struct PackArgsH3 { PackSegH3 seg[PACK_BATCH]; uint32_t* dst; };
+struct PackArgsH3 { PackSegH3 seg[PACK_BATCH]; uint32_t* dst; uint32_t* range; };
 
 __device__ __forceinline__ float seg_value(const PackSegH3& s, int n, int c) {
     if (c < s.n0) return s.src[(long long)n * s.ld + s.s0 + c];
@@ -1772,14 +1792,18 @@ __global__ void nsff_pack_kernel_h3(const PackArgsH3 a) {
         if (n < 0 || n >= s.nrows) return;            // other rows stay zero (buffer is memset first)
     }
     h8 out;
+    float rm = 0.f;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         const int c = ks * 16 + 8 * (lane >> 5) + t;
         const float x = s.kind == 1 ? seg_value(s, n, c) : s.src[(long long)n * s.ld + c];
+        rm = nsff_absmax3(rm, x, x);
         const _Float16 hi = (_Float16)x;
         out[t] = part == 0 ? hi : (_Float16)(x - (float)hi);
     }
     reinterpret_cast<h8*>(a.dst + s.dst)[idx] = out;
+    // (behind the early returns: the ballot covers the lanes that split something)
+    nsff_range_flag(a.range, rm, NSFF_RANGE_PARAMS);
 }
 
 // Folded head rows (see NsffLayoutH3): out_w[r][i] = sum_o W_head[r][o] * W_final[o][i],  out_b[r] = sum_o W_head[r][o] *
@@ -1898,6 +1922,7 @@ int nsff_h3_pack_weights(const NsffModelDesc* desc, const float* const* params, 
     for (size_t base = 0; base < segs.size(); base += PACK_BATCH) {
         PackArgsH3 pa{};
         pa.dst = reinterpret_cast<uint32_t*>(packed);
+        pa.range = nsff_range_word(st);
         const int n = (int)std::min<size_t>(PACK_BATCH, segs.size() - base);
         int max_threads = 0;
         for (int i = 0; i < n; ++i) {
@@ -1975,6 +2000,7 @@ int nsff_h3_fold_heads(const NsffModelDesc* desc, const float* const* params, vo
     uint32_t* pw = reinterpret_cast<uint32_t*>(packed);
     PackArgsH3 pf{};
     pf.dst = pw;
+    pf.range = nsff_range_word(st);
     int nf = 0;
     auto fold = [&](FoldArgs& f, uint32_t scratch, uint32_t tile, uint32_t bias) {
         f.out_w = reinterpret_cast<float*>(pw + scratch); f.out_b = reinterpret_cast<float*>(pw + bias);
@@ -2333,11 +2359,13 @@ int g_nsff_last_h3_grid = 0;          // workgroups of that launch when it was a
 // a ray's samples).  The hand-scheduled training forward never sees these columns (they arrive as bias rows): one 16-byte store per
 // thread and block here instead.
 namespace {
-struct SideTileArgs { const float* dir_emb; const float* a_emb; _Float16* out; long long n_points; int pts_per_ray, in_dir, in_a, side_rows; };
+struct SideTileArgs { const float* dir_emb; const float* a_emb; _Float16* out; long long n_points; int pts_per_ray, in_dir, in_a, side_rows;
+                     uint32_t* range; };
 __global__ __launch_bounds__(256) void nsff_side_tile_kernel(const SideTileArgs a) {
     const long long tile = blockIdx.x, p0 = tile * 64;
     const int lane = threadIdx.x & 63, rblocks = a.side_rows >> 5;
     _Float16* dst = a.out + tile * (64LL * a.side_rows);
+    float rm = 0.f;                                   // value-domain check of the codes (NSFF_RANGE_CODES)
     for (int blk = threadIdx.x >> 6; blk < 4 * rblocks; blk += 4) {
         const int ks = blk / rblocks, rb = blk % rblocks;
         const int row = 32 * rb + (lane & 31), pt0 = 16 * ks + 8 * (lane >> 5);
@@ -2351,10 +2379,12 @@ __global__ __launch_bounds__(256) void nsff_side_tile_kernel(const SideTileArgs 
                 if (row < a.in_dir) v = a.dir_emb[ray * a.in_dir + row];
                 else if (row < a.in_dir + a.in_a) v = a.a_emb[ray * a.in_a + (row - a.in_dir)];
             }
+            rm = nsff_absmax3(rm, v, v);
             out[t] = (_Float16)v;
         }
         *reinterpret_cast<h8*>(dst + (((long long)ks * rblocks + rb) * 64 + lane) * 8) = out;
     }
+    nsff_range_flag(a.range, rm, NSFF_RANGE_CODES, (unsigned)lane);
 }
 }  // namespace
 
@@ -2369,6 +2399,7 @@ int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const Nsf
     if (g.xyz && 3 + 6 * g.n_freqs != d.in_xyz) return NSFF_ERR_INVALID;
     k.packed = reinterpret_cast<const uint32_t*>(packed);
     k.span = span;
+    k.range = nsff_range_word(st);
     k.xyz = g.xyz; k.x_emb = g.x_emb; k.dir_emb = g.dir_emb; k.a_emb = g.a_emb; k.t_emb = g.t_emb;
     k.raw = g.raw; k.n_points = g.n_points; k.pts_per_ray = g.pts_per_ray;
     k.save_acts = reinterpret_cast<_Float16*>(g.save_acts);
@@ -2466,7 +2497,7 @@ int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const Nsf
             if (side) {
                 ka.sig_b_off = k.L.s_sigma_b;
                 if (k.save_side != nullptr) {
-                    SideTileArgs sa{g.dir_emb, g.a_emb, k.save_side, g.n_points, g.pts_per_ray, d.in_dir, d.in_a, k.side_rows};
+                    SideTileArgs sa{g.dir_emb, g.a_emb, k.save_side, g.n_points, g.pts_per_ray, d.in_dir, d.in_a, k.side_rows, k.range};
                     hipLaunchKernelGGL(nsff_side_tile_kernel, dim3((unsigned)k.n_tiles), dim3(256), 0, st, sa);
                 }
             }

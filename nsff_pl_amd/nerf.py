@@ -20,6 +20,7 @@ from torch import nn
 
 from . import _lib
 from . import packing
+from . import range_check
 
 # Raw output slot order of the field kernel (one 16-float record per point).
 SLOT_RGB_S, SLOT_SIGMA_S, SLOT_RGB_T, SLOT_SIGMA_T, SLOT_FW, SLOT_BW = 0, 3, 4, 7, 8, 11
@@ -125,9 +126,15 @@ class NeRF(nn.Module):
 
         ``x`` holds already-embedded rows ``[xyz | dir | a | t]`` (or ``[xyz | t]`` /
         ``[xyz]`` when ``sigma_only``); the rows go to the field kernel in its
-        "pre-embedded input" mode.
+        "pre-embedded input" mode.  ``config.set_range_check`` decides what happens when f16x3 operands left the fp16
+        range ("fallback": the call -- deterministic, and without an autograd graph -- runs again in "f32").
         """
         _lib.require_gpu_tensor(x, "NeRF input")
+        return range_check.checked("NeRF.forward", x.device,
+                                   lambda: self._forward(x, sigma_only, output_static, output_transient, output_transient_flow),
+                                   can_fallback=True)
+
+    def _forward(self, x, sigma_only, output_static, output_transient, output_transient_flow):
         x = x.contiguous().float()
         B = x.shape[0]
         cx, cd, ca, ct = self.in_channels_xyz, self.in_channels_dir, self.in_channels_a, self.in_channels_t

@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from . import autograd
 from . import config
+from . import range_check
 from . import field_grad
 from . import ray_geometry
 
@@ -391,8 +392,14 @@ def render_rays(models,
     Results are fresh contiguous fp32 GPU tensors computed by the HIP kernels.  With autograd enabled,
     ``test_time=False`` and parameters that require grad, the results carry a graph to the model /
     embedding parameters (see :mod:`nsff_pl_amd.autograd`).
+    ``config.set_range_check`` decides what happens when f16x3 operands left the fp16 range during the call ("fallback":
+    a ``test_time`` call without perturbation or noise is rendered again in "f32").
     """
-    return _render_rays(models, embeddings, rays, ts, max_t, N_samples, perturb, noise_std, N_importance, chunk, test_time, kwargs)
+    _lib.require_gpu_tensor(rays, "rays")
+    return range_check.checked(
+        "render_rays", rays.device,
+        lambda: _render_rays(models, embeddings, rays, ts, max_t, N_samples, perturb, noise_std, N_importance, chunk, test_time, kwargs),
+        can_fallback=bool(test_time) and perturb == 0 and noise_std == 0)
 
 
 def _render_rays(models, embeddings, rays, ts, max_t, N_samples, perturb, noise_std, N_importance, chunk, test_time, kwargs,

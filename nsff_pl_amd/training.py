@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from . import field_grad
 from . import metrics
+from . import range_check
 from .autograd import grad_parameters
 from .losses import NeRFWLoss
 from .optim import FlatAdam
@@ -241,16 +242,37 @@ class NSFFTrainer:
             self._resolve_graph(batch)
         if self.graph:
             return self._graph_step(batch)
-        self._setup_flat_grads()
-        field_grad.drop_stale_pending()
-        self.zero_grad()
-        loss, log = self.training_step(batch)
-        with field_grad.deferred_weight_grads():
-            loss.backward()
+        check = self._range_begin()
+        with range_check.suppressed():
+            self._setup_flat_grads()
+            field_grad.drop_stale_pending()
+            self.zero_grad()
+            loss, log = self.training_step(batch)
+            with field_grad.deferred_weight_grads():
+                loss.backward()
         self.allreduce()
+        self._range_end(check)
         self.optimizer.step()
         self._invalidate_packs()
         return log
+
+    def _range_begin(self):
+        """config.set_range_check: clear the device's value-domain word in front of the step (outside any capture); the
+        mode, or "off" """
+        mode = range_check.active()
+        if mode != "off":
+            range_check.range_flags(self._flat_grad.device, clear=True)
+        return mode
+
+    def _range_end(self, mode):
+        """Behind the gradient all-reduce, in front of Adam: a flagged step (on any rank: the flags are all-reduced first, so
+        that every rank decides alike) warns, or raises with the weights and the optimizer state untouched."""
+        if mode == "off":
+            return
+        dev = self._flat_grad.device
+        flags = range_check.all_ranks(range_check.range_flags(dev, clear=False), dev)
+        if flags:
+            range_check.report(flags, "NSFFTrainer.step", "warn" if mode == "warn" else "raise", stacklevel=4)
 
     AUTO_GRAPH_POINT_EVALS = 450_000        # (see __init__: where the eager step stops being bound by the host)
 
@@ -274,6 +296,19 @@ class NSFFTrainer:
         return log
 
     def _graph_step(self, batch):
+        with range_check.suppressed():
+            self._graph_capture(batch)
+        for k, v in self._static_batch.items():
+            v.copy_(batch[k])
+        check = self._range_begin()             # (between the replays: never inside a capture)
+        self._graph.replay()
+        self.allreduce()                        # outside the captures: RCCL is not captured
+        self._range_end(check)
+        self._graph_opt.replay()
+        self._invalidate_packs()
+        return self._static_log
+
+    def _graph_capture(self, batch):
         if self._graph is None:
             if self._geo is None:
                 self.on_train_epoch_start(self.current_epoch)
@@ -300,13 +335,6 @@ class NSFFTrainer:
                 for p, k in zip(self.params, keep):
                     p.copy_(k)
             self.optimizer.load_state_dict(keep_opt)
-        for k, v in self._static_batch.items():
-            v.copy_(batch[k])
-        self._graph.replay()
-        self.allreduce()                        # outside the captures: RCCL is not captured
-        self._graph_opt.replay()
-        self._invalidate_packs()
-        return self._static_log
 
     # utils/__init__.py:82-104 + PL checkpoint layout (train.py:55,59,76,87): nerf_fine. / nerf_coarse. / embedding_t. / embedding_a.
     def checkpoint(self):

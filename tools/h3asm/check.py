@@ -25,6 +25,7 @@ PH_BASE = 0x2_0000_0000
 T_BASE = 0x3_0000_0000
 ACT_BASE = 0x4_0000_0000                   # SAVE build: activation slots (slot, tile64, 4 ks, 256 rows, 16 points) fp16
 MASK_BASE = 0x5_0000_0000                  # SAVE build: sign words (slot, tile64, 256 threads) uint64
+FLAG_BASE = 0x6_0000_0000                  # the value-domain word (NSFF_RANGE_*)
 N_TILES64 = 6                              # the simulated workgroup is 128-point tile 1 of 3: 64-point tiles 2 and 3
 LDS_X = 0
 LDS_RAW = 2 * gen.PLANE_B                  # raw-record image: 128 points x 16 floats
@@ -288,10 +289,15 @@ def head_reference(case, xh_, xl_):
     return ((c[0] + c[1]).astype(np.float32) + c[2]).astype(np.float32)[:, :hd["n_rows"]]
 
 
-def run_case(kind, seed=0, verbose=True):
+def run_case(kind, seed=0, verbose=True, poke=None):
+    """poke (or None): a value put into neuron 5 of layer 0's bias row -- the tile's activations of that neuron leave the fp16
+    range when it is large; the run then returns the value-domain word the body left instead of checking the arithmetic."""
     save = kind.endswith("_save")
     persist = kind.endswith("_persist")
     case = make_case(kind[:-5] if save else (kind[:-8] if persist else kind), seed)
+    if poke is not None:
+        case["rows"][0] = case["rows"][0].copy()
+        case["rows"][0][5] = np.float32(poke)
     pre, prog, _ = gen.build(save=save)
     sim = Sim(pre + prog)                      # the two asm statements back to back (the encoder between them is C++)
     sim.add_buffer(PK_BASE, case["pk"])
@@ -305,6 +311,8 @@ def run_case(kind, seed=0, verbose=True):
         sim.add_buffer(ACT_BASE, acts)
         sim.add_buffer(MASK_BASE, masks)
         sim.mem_written = {ACT_BASE: np.zeros(acts.size, bool), MASK_BASE: np.zeros(masks.size, bool)}
+    flag = np.zeros(4, np.uint32)
+    sim.add_buffer(FLAG_BASE, flag)
     sim.add_buffer(PH_BASE, phases.reshape(-1))
     sim.add_buffer(T_BASE, case["t_table"].reshape(-1).view(np.uint32))
     # LDS: input tile as the encoder leaves it (hi / lo planes), bias table
@@ -322,7 +330,7 @@ def run_case(kind, seed=0, verbose=True):
     I_S, I_V = gen.IN_S, gen.IN_V
     for w in sim.waves:
         tid = 64 * w.id + np.arange(64)
-        for name, val in (("pk", PK_BASE), ("phases", PH_BASE)):
+        for name, val in (("pk", PK_BASE), ("phases", PH_BASE), ("rflag", FLAG_BASE)):
             w.s[I_S[name].i], w.s[I_S[name].i + 1] = val & 0xFFFFFFFF, val >> 32
         for name, val in (("lds", LDS_X), ("biaslds", LDS_BIAS), ("wave", w.id), ("in_t", body_in_t), ("rawlds", LDS_RAW), ("n1", phases[0][3]),
                           ("r1", phases[0][4]), ("r1w", phases[0][5]), ("r2", phases[0][6]), ("r2w", phases[0][7])):
@@ -343,6 +351,9 @@ def run_case(kind, seed=0, verbose=True):
     t0 = time.time()
     sim.run()
     dt = time.time() - t0
+    if poke is not None:
+        return int(flag[0])
+    assert flag[0] == 0, "a tile inside the fp16 range set the value-domain word"
     # result: the last activation in the two planes
     got = np.zeros((128, 256), np.float32)
     for r in range(128):

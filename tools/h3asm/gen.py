@@ -21,6 +21,7 @@ simulator.  Register map (asm-owned; the compiler keeps v0..v23, s0..s39 and VCC
     v24..v39  addresses      v40..v63 epilogue temporaries     v64..v95 input stash     v96..v111 XH[2][2] fragments
     v112..v119 XL[2]         v120..v127 spare                  v128..v191 acc_A         v192..v255 acc_B
     a[16 j .. 16 j + 15] weight slot j = k-step j of the resident segment: [mt0 hi | mt0 lo | mt1 hi | mt1 lo] x 4 registers
+    s72, s[94:97], v63 in the epilogue streams: the value-domain check (S_LIM, S_RTMP, S_RACC, V_RMAX below)
 """
 import os
 import sys
@@ -53,6 +54,15 @@ S_SAVE = S(48, 2)
 S_R1, S_R2, S_SEL = S(50), S(51), S(52)
 S_T0, S_T1 = S(53), S(54)
 S_RAWLDS = S(55)            # byte address of the raw-record image in LDS (the heads' pre-activation sums go there)
+# the value-domain check (NSFF_RANGE_ACT / NSFF_RANGE_SAVED): every epilogue stream folds its post-ReLU values into a running
+# maximum V_RMAX (four v_max3 per unit of eight values) and ORs the lanes whose maximum is not <= 65504 into S_RACC (seeded by the
+# encoder's own maximum, %[rm0]); behind the last phase the lanes of S_RACC -- if any -- OR the build's bit into the word at %[rflag]
+# with ONE exec-masked global_atomic_or (null: nothing).  V_RMAX = v63: no body that carries an epilogue touches it otherwise.
+S_LIM = S(72)               # 65504.0
+S_RTMP, S_RACC = S(94, 2), S(96, 2)
+V_RMAX = V(63)
+F16_MAX_BITS = 0x477FE000
+RANGE_BIT = {False: 0x1, True: 0x2}          # NSFF_RANGE_ACT (inference body), NSFF_RANGE_SAVED (the SAVE build)
 S_CUR = 56                  # s56..s63 current descriptor
 S_NXT = 64                  # s64..s71 next descriptor (being fetched)
 D_BODY, D_FLAGS, D_BIAS, D_N1, D_R1, D_R1W, D_R2, D_R2W = range(8)
@@ -243,7 +253,23 @@ def epilogue_unit(half, u, tset, sig=False):
     if SAVE and u in (3, 7):   # word mt complete: lane's 4 bytes at S_MASK + 8 (lane) + 4 mt (+ 2 KiB: the tile of half B)
         out += [I_valu("v_lshrrev_b32", V_TMP, 1, V_LANE16),
                 _nt(I_gstore_s(V_TMP, V_MSKW, S_MASK, 4 * mt + (2048 if half == "B" else 0)))]
-    return out
+    return range_check_unit(out, x, H, u)
+
+
+def range_check_unit(out, x, H, u):
+    """The value-domain check of a unit's eight post-ReLU values (see S_LIM): V_RMAX = max(V_RMAX, x[2k], x[2k + 1]) beside hi
+    conversion k (x is still whole there); unit 0 starts the stream's maximum at 0, unit 7 compares it and ORs the verdict into
+    S_RACC behind its last instruction.  Each goes out as a BUNDLE with the instruction it follows (a list item: emit_ride), so
+    the ride keeps its item count and every other instruction its place in the schedule."""
+    chk = {repr(H[k]): I_v_max3(V_RMAX, V_RMAX, x[2 * k], x[2 * k + 1]) for k in range(4)}
+    res = [[i, chk[repr(i.args["d"])]] if isinstance(i, Inst) and i.op == "v_cvt_pkrtz_f16_f32" and repr(i.args["d"]) in chk else i
+           for i in out]
+    if u == 0 and res:
+        res[0] = [I_valu("v_mov_b32", V_RMAX, 0)] + (res[0] if isinstance(res[0], list) else [res[0]])
+    if u == 7 and res:
+        res[-1] = (res[-1] if isinstance(res[-1], list) else [res[-1]]) + [
+            I_v_cmp_nge_f32_s(S_RTMP, S_LIM, V_RMAX), I_salu("s_or_b64", S_RACC, S_RACC, S_RTMP, scc=True)]
+    return res
 
 
 def _nt(store):
@@ -457,8 +483,11 @@ def emit_rebuild(s, part, first):
 
 
 def emit_ride(s, item):
-    """a riding item: an instruction, (instruction, tag) or the marker ('NEED_LDS', tag)"""
-    if isinstance(item, tuple) and item[0] == "NEED_LDS":
+    """a riding item: an instruction, a bundle [instructions] (range_check_unit), (instruction, tag) or the marker ('NEED_LDS', tag)"""
+    if isinstance(item, list):
+        for i in item:
+            s.emit(i, "ride")
+    elif isinstance(item, tuple) and item[0] == "NEED_LDS":
         s.need_lds(item[1])
     elif isinstance(item, tuple):
         s.emit(item[0], item[1])
@@ -747,9 +776,9 @@ def bare_epilogue(name, half):
                     for i in hl[g]:
                         s.emit(i, "head")
                     g += 1
-            s.emit(x, "ride")
+            emit_ride(s, x)
             if y is not None:
-                s.emit(y, "ride")
+                emit_ride(s, y)
     if SAVE:                # (the sign words of half B of the last layer were the slot's last: epilogue_stream's pointer step is not needed)
         pass
     while g < len(hl):
@@ -782,8 +811,8 @@ def raw(text, wr=(), rd=()):
 
 # Inline-asm operands and the registers the simulator's harness presets in their place
 IN_S = dict(pk=S(0, 2), phases=S(2, 2), lds=S(4), biaslds=S(5), wave=S(6), in_t=S(7), r1=S(8), r1w=S(9), r2=S(10), r2w=S(11), n1=S(12),
-            rawlds=S(13), act=S(14, 2), mask=S(16, 2), astride=S(18), mstride=S(19))
-IN_V = dict(tid=V(0), tpa0=V(1), tpa1=V(2), tpb0=V(3), tpb1=V(4))
+            rawlds=S(13), act=S(14, 2), mask=S(16, 2), astride=S(18), mstride=S(19), rflag=S(20, 2))
+IN_V = dict(tid=V(0), tpa0=V(1), tpa1=V(2), tpb0=V(3), tpb1=V(4), rm0=V(5))
 
 
 def in_s(dst, name):
@@ -827,6 +856,9 @@ def prologue():
     e(in_s(S_PK, "pk")); e(in_s(S_PH, "phases")); e(in_s(S_LDS, "lds")); e(in_s(S_BIASLDS, "biaslds"))
     e(in_s(S_WAVE, "wave")); e(in_s(S_INT, "in_t")); e(in_s(S_RAWLDS, "rawlds")); e(in_v(V_TMP, "tid"))
     e(in_v(V(34), "tpa0")); e(in_v(V(35), "tpa1")); e(in_v(V(36), "tpb0")); e(in_v(V(37), "tpb1"))
+    # value-domain check: the flag word's address, the limit, the encoder's maximum |x| of this lane (%[rm0]) as the first verdict
+    e(I_salu("s_mov_b32", S_LIM, F16_MAX_BITS)); e(in_v(V(T0 + 6), "rm0"))
+    e(I_v_cmp_nge_f32_s(S_RACC, S_LIM, V(T0 + 6)))
     if not SAVE:
         # the NEXT tile's point of this thread (a persistent workgroup's tile loop, field_h3.hip): %[nxa] v64 its address, %[nx0..2]
         # three of the compiler's registers (outputs of the statement, valid behind L_end's vmcnt(0)).  Not in the wait model:
@@ -939,6 +971,20 @@ def dispatcher():
     return o
 
 
+def range_flag_tail():
+    """Behind the last phase: the lanes in S_RACC (a value outside the fp16 range reached one of their splits) OR the build's bit
+    into the flag word -- one exec-masked vector atomic, issued only when some lane saw such a value and the word's address is set."""
+    rflag = IN_S["rflag"]           # (%[rflag]: an input operand -- the compiler's registers stay untouched by the body)
+    atomic = I_gatomic_or_s(V_OFF, V_TMP, rflag)
+    atomic.text = f"global_atomic_or {V_OFF}, {V_TMP}, %[rflag]"
+    return [I_s_cmp("s_cmp_lg_u64", S_RACC, 0), I_branch("s_cbranch_scc0", "L_range_done"),
+            Inst("s_cmp_lg_u64", "s_cmp_lg_u64 %[rflag], 0", [rflag], [], "salu", dict(a=rflag, b=0)),
+            I_branch("s_cbranch_scc0", "L_range_done"),
+            I_s_mov_exec(S_RACC), I_valu("v_mov_b32", V_OFF, 0), I_valu("v_mov_b32", V_TMP, RANGE_BIT[SAVE]),
+            atomic, I_s_mov_exec(-1),       # (the body runs with every lane on)
+            I_label("L_range_done")]
+
+
 def build(save=False):
     """-> (pre-issue statement, main statement, bodies); save: the training-forward body (see SAVE)"""
     global SAVE
@@ -982,6 +1028,7 @@ def _build():
     prog += dispatcher()
     prog.append(I_label("L_end"))
     prog.append(I_wait(vm=0, lgkm=0))
+    prog += range_flag_tail()
     if TIMING:
         prog += timing_store() + [I_wait(vm=0, lgkm=0)]
     return pre_issue(), prog, bodies

@@ -164,6 +164,23 @@ def I_gload_x4_v(d, vaddr, off=0):
                 dict(d=d, vaddr=vaddr, off=off))
 
 
+def I_gatomic_or_s(voff, data, sbase):
+    """global_atomic_or voff, data, s[base:base+1]  (address = sbase + zext(voff); no return value): the value-domain flag word"""
+    assert data.n == 1 and sbase.n == 2
+    return Inst("gatomic_or_s", f"global_atomic_or {voff}, {data}, {sbase}", [voff, data, sbase], [], "vmem",
+                dict(data=data, voff=voff, sbase=sbase))
+
+
+def I_v_max3(d, a, b, c):                # d = max(a, b, c), fp32 (a NaN operand is dropped, as v_max_f32 does)
+    return I_valu("v_max3_f32", d, a, b, c)
+
+
+def I_v_cmp_nge_f32_s(d, a, b):          # s[d:d+1] = lanes with !(a >= b)  (VOP3: a an SGPR, b a VGPR; NaN compares true)
+    assert d.f == "s" and d.n == 2
+    return Inst("v_cmp_nge_f32", f"v_cmp_nge_f32_e64 {d}, {_src(a)}, {b}", [x for x in (a, b) if _is_reg(x)], [d], "valu",
+                dict(d=d, a=a, b=b))
+
+
 def I_valu(op, d, *srcs, text=None, extra_wr=()):
     t = text or f"{op} {d}, " + ", ".join(_src(s) for s in srcs)
     return Inst(op, t, [s for s in srcs if _is_reg(s)], [d] + list(extra_wr), "valu", dict(d=d, s=list(srcs)))
@@ -558,6 +575,24 @@ class Sim:
             self._lds_access(w, addr, n_dw, True, data)
             w.lds_q.append(set())
             return None
+        if k == "vmem" and ins.op == "gatomic_or_s":
+            base = int(w.s[a["sbase"].i]) | (int(w.s[a["sbase"].i + 1]) << 32)
+            addr = base + self._rv(w, a["voff"]).astype(np.uint64)
+            for l in range(NL):
+                if not w.exec[l]:
+                    continue
+                hit = False
+                for b0, arr in self.mem.items():
+                    if b0 <= int(addr[l]) and int(addr[l]) + 4 <= b0 + arr.size * 4:
+                        if (int(addr[l]) - b0) % 4:
+                            raise SimError(f"unaligned global atomic ({ins.text})")
+                        arr[(int(addr[l]) - b0) // 4] |= self._rv(w, a["data"])[l]
+                        hit = True
+                if not hit:
+                    raise SimError(f"wave {w.id} pc {w.pc}: `{ins.text}` touches unmapped global memory (lane {l}, address {int(addr[l]):#x})")
+            self.n_atomics = getattr(self, "n_atomics", 0) + 1
+            w.vm_q.append(set())
+            return None
         if k == "vmem" and ins.op == "gstore_s":
             base = int(w.s[a["sbase"].i]) | (int(w.s[a["sbase"].i + 1]) << 32)
             addr = base + self._rv(w, a["voff"]).astype(np.uint64) + np.uint64(a["off"])
@@ -642,6 +677,14 @@ class Sim:
             self._wv(w, a["a"], nx, masked=False)
             self._wv(w, a["b"], ny, masked=False)
             return
+        if op == "v_cmp_nge_f32":
+            r = ~(self._val(w, a["a"]).view(np.float32) >= self._val(w, a["b"]).view(np.float32))
+            bits = 0
+            for l in range(NL):
+                if r[l] and w.exec[l]:
+                    bits |= 1 << l
+            w.s[a["d"].i], w.s[a["d"].i + 1] = bits & 0xFFFFFFFF, bits >> 32
+            return
         if op in ("v_cmp_lt_u32", "v_cmp_gt_u32"):
             r = self._val(w, a["a"]) < self._val(w, a["b"]) if op == "v_cmp_lt_u32" else self._val(w, a["a"]) > self._val(w, a["b"])
             bits = 0
@@ -653,6 +696,8 @@ class Sim:
         d, s = a["d"], [self._val(w, x) for x in a["s"]]
         if op == "v_max_f32":
             out = np.maximum(f32(s[0]), f32(s[1])).view(np.uint32)
+        elif op == "v_max3_f32":
+            out = np.fmax(np.fmax(f32(s[0]), f32(s[1])), f32(s[2])).astype(np.float32).view(np.uint32)
         elif op == "v_cvt_pkrtz_f16_f32":
             out = f16_rtz_pack(f32(s[0]), f32(s[1]))
         elif op == "v_fma_mix_lo":
@@ -749,6 +794,16 @@ class Sim:
             x, y = self._sval(w, a["a"]), self._sval(w, a["b"])
             w.scc = int({"s_cmp_lt_u32": x < y, "s_cmp_gt_u32": x > y, "s_cmp_eq_u32": x == y, "s_cmp_lg_u32": x != y,
                          "s_cmp_ge_u32": x >= y, "s_cmp_le_u32": x <= y}[op])
+            return
+        if op == "s_cmp_lg_u64":
+            val = lambda x: (int(w.s[x.i]) | (int(w.s[x.i + 1]) << 32)) if isinstance(x, Reg) else int(x)
+            w.scc = int(val(a["a"]) != val(a["b"]))
+            return
+        if op == "s_or_b64":
+            val = lambda x: (int(w.s[x.i]) | (int(w.s[x.i + 1]) << 32)) if isinstance(x, Reg) else int(x) & ((1 << 64) - 1)
+            r = val(a["s"][0]) | val(a["s"][1])
+            w.s[a["d"].i], w.s[a["d"].i + 1] = r & 0xFFFFFFFF, r >> 32
+            w.scc = int(r != 0)
             return
         if op == "s_bitcmp1_b32":
             w.scc = (self._sval(w, a["a"]) >> (self._sval(w, a["b"]) & 31)) & 1
