@@ -323,6 +323,18 @@ int nsff_last_bwd_grid(void);
 int nsff_field_bwd_phase_program(const NsffModelDesc* desc, int32_t dynamic, int32_t want_xin, int64_t n_tiles, uint32_t* out,
                                  int32_t max_phases, uint32_t* seg_offsets, int32_t max_segs);
 
+/* Host-only, as nsff_field_launch_plan: what nsff_field_backward would launch on a device of n_cus compute units.
+ * kernel_override: 'c' as NSFF_BWD_KERNEL=c, else 0; persist: 0 as NSFF_BWD_PERSIST=0, else 1.  Returns the nsff_last_bwd_kernel
+ * code (0 c, 1 h3b, 2 c+h3b, 3 x3) or the call's negative error (n_points == 0: NSFF_OK, no record).  out: max_launches (>= 2)
+ * records of NSFF_PLAN_WORDS int32: [0] NSFF_BWD_LAUNCH_* kernel, [1] workgroups (a persistent launch falls back to [4] when no
+ * counter word can be had), [2] threads, [3] trunks (1 static, 2 dynamic, 3 both), [4] (tile, trunk) items, [5] 1 = persistent: the
+ * launch takes an item counter, [6] steps of the launch's step program, [11] FNV-1a of the argument bytes (counter null). */
+#define NSFF_BWD_LAUNCH_C    1   /* nsff_field_bwd_kernel      */
+#define NSFF_BWD_LAUNCH_H3B  2   /* nsff_field_bwd_kernel_h3b  */
+#define NSFF_BWD_LAUNCH_X3   3   /* nsff_field_bwd_kernel_x3   */
+int nsff_field_bwd_launch_plan(const NsffModelDesc* desc, const NsffFieldBwdArgs* args, int32_t n_cus, int32_t kernel_override,
+                               int32_t persist, int32_t* out, int32_t max_launches);
+
 /* d_xin (P, xin_rows) of nsff_field_backward -> gradient w.r.t. the points (derivative of PosEmbedding, reference
  * nerf.py:17-30) and w.r.t. the per-ray time codes (sum over the ray's pts_per_ray consecutive points, the repeat of
  * rendering.py:168).  d_xyz (P,3) / d_t (n_rays, in_t): either may be NULL.  freqs_host: HOST array.                */
@@ -744,6 +756,26 @@ int         nsff_last_field_grid(void);
  * first segments' weight slots 0..7 for the workgroup's next tile (n_phases[t] = 0 for a trunk that ends with a skip layer). */
 int         nsff_field_phase_program(const NsffModelDesc* desc, int static_mode, int transient_mode, int fold_t, uint32_t* steps,
                              int* n_steps, int* n_static_steps, uint32_t* phases_static, uint32_t* phases_dynamic, int* n_phases);
+
+/* Host-only (no GPU work; the pointers of `args` are tested against null and for alignment, never read): what nsff_field_query
+ * would launch for these arguments on a device of n_cus compute units (no_persist != 0: as under NSFF_NO_PERSIST=1).  Only the
+ * dispatcher's own checks run, not nsff_field_query's argument checks; `packed` and the stream are not part of the decision.
+ * Returns the NSFF_KERNEL_* code nsff_last_field_kernel would report, or the dispatcher's negative error.  out: room for
+ * max_launches (>= 3) records of NSFF_PLAN_WORDS int32, in issue order, unused records zeroed:
+ *   [0] NSFF_LAUNCH_* kernel, [1] workgroups, [2] threads per workgroup, [3] p_mode (0 one workgroup per tile; 1..4 the persistent
+ *   forms: one trunk / both by XCD / the dynamic trunk beside an eight-wave static launch / both, unequal cost), [4] p_tiles,
+ *   [5] p_split, [6] p_long, [7] split_trunks, [8] grid_tiles, [9] time-bias rows in use (NsffFieldArgs::t_bias), [10] side-bias
+ *   rows in use (s_bias), [11] FNV-1a (32 bit) of the kernel's argument bytes -- equal words mean equal launches.           */
+#define NSFF_PLAN_WORDS 12
+#define NSFF_LAUNCH_SIDE_TILE      1   /* nsff_side_tile_kernel: save_side from the per-ray codes                  */
+#define NSFF_LAUNCH_H3_64          2   /* nsff_field_kernel_h3, 64-point tiles                                    */
+#define NSFF_LAUNCH_H3_64_SAVE     3   /* ... its training forward                                                */
+#define NSFF_LAUNCH_H3_8WAVE       4   /* nsff_field_kernel_h3, 128-point tiles, eight waves                      */
+#define NSFF_LAUNCH_H3_8WAVE_SAVE  5   /* ... its training forward                                                */
+#define NSFF_LAUNCH_H3A            6   /* nsff_field_kernel_h3a                                                   */
+#define NSFF_LAUNCH_H3A_SAVE       7   /* nsff_field_kernel_h3a_save                                              */
+int         nsff_field_launch_plan(const NsffModelDesc* desc, const NsffFieldArgs* args, int32_t n_cus, int32_t no_persist,
+                                   int32_t* out, int32_t max_launches);
 
 /* ---- f16x3 value-domain flag ----
  * The f16x3 kernels carry every fp32 operand as hi + lo halfs with hi = rtz_f16(x): exact to fp32 rounding only while

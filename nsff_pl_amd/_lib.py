@@ -185,6 +185,7 @@ _SIGNATURES = {
     "nsff_last_field_grid": (C.c_int, []),
     "nsff_field_phase_program": (C.c_int, [C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int),
                                    C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "nsff_field_launch_plan": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(FieldArgs), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "nsff_time_bias_rows": (C.c_int, [C.POINTER(ModelDesc)]),
     "nsff_time_bias": (C.c_int, [C.POINTER(TimeBiasJob), C.c_int32, C.c_int64, C.c_void_p]),
     "nsff_rng_draws": (C.c_int, [C.POINTER(RngJob), C.c_int32, C.c_uint64, C.c_void_p]),
@@ -227,6 +228,8 @@ _SIGNATURES = {
     "nsff_last_bwd_grid": (C.c_int, []),
     "nsff_field_bwd_phase_program": (C.c_int, [C.POINTER(ModelDesc), C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_uint32), C.c_int32,
                                                 C.POINTER(C.c_uint32), C.c_int32]),
+    "nsff_field_bwd_launch_plan": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(FieldBwdArgs), C.c_int32, C.c_int32, C.c_int32,
+                                             C.POINTER(C.c_int32), C.c_int32]),
     "nsff_fold_grads": (C.c_int, [C.POINTER(FoldGradArgs), _fp]),
     "nsff_fold_grads_dense": (C.c_int, [C.POINTER(FoldDenseArgs), _fp]),
     "nsff_pack_weights_bwd_ex": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(_fp), _fp, _fp, _fp]),
@@ -730,6 +733,28 @@ def last_bwd_kernel():
 def last_bwd_grid():
     """workgroups of the last hand-scheduled data-gradient launch (= compute units for a persistent one; 0: none)"""
     return load().nsff_last_bwd_grid()
+
+
+PLAN_WORDS = 12            # NSFF_PLAN_WORDS
+
+
+def field_launch_plan(desc, args, n_cus, no_persist=False):
+    """Host-only: what nsff_field_query would launch for (ModelDesc, FieldArgs) on a device of n_cus compute units ->
+    (NSFF_KERNEL_* code or negative error, [record of PLAN_WORDS ints per launch]) -- include/nsff_render.h::nsff_field_launch_plan."""
+    out = (C.c_int32 * (3 * PLAN_WORDS))()
+    code = load().nsff_field_launch_plan(C.byref(desc), C.byref(args), int(n_cus), int(bool(no_persist)), out, 3)
+    recs = [list(out[i * PLAN_WORDS:(i + 1) * PLAN_WORDS]) for i in range(3)]
+    return code, [r for r in recs if r[0] != 0]
+
+
+def field_bwd_launch_plan(desc, args, n_cus, kernel_override=None, persist=True):
+    """Host-only: what nsff_field_backward would launch (kernel_override "c" as NSFF_BWD_KERNEL=c, persist False as
+    NSFF_BWD_PERSIST=0) -> (0 c / 1 h3b / 2 c+h3b / 3 x3 or negative error, records) -- nsff_field_bwd_launch_plan."""
+    out = (C.c_int32 * (2 * PLAN_WORDS))()
+    code = load().nsff_field_bwd_launch_plan(C.byref(desc), C.byref(args), int(n_cus), ord(kernel_override) if kernel_override else 0,
+                                                      int(bool(persist)), out, 2)
+    recs = [list(out[i * PLAN_WORDS:(i + 1) * PLAN_WORDS]) for i in range(2)]
+    return code, [r for r in recs if r[0] != 0]
 
 
 def field_bwd_phase_program(model, dynamic, want_xin, n_tiles, max_phases=32):

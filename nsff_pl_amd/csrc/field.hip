@@ -660,11 +660,7 @@ int nsff_field_query(const NsffModelDesc* desc, const void* packed_v, const Nsff
     }
     hipError_t e = hipSuccess;
     if (g.precision == NSFF_PREC_F16X3) {
-        // default tiling: 128 points as eight waves of 32 neurons (one workgroup per CU, every weight byte fetched once per
-        // 128 points, no spilled registers: 41 MB instead of 79 MB of HBM traffic per C2 launch and -0.8 % time); launches
-        // too small to give every CU such a tile keep the 64-point tiling (two workgroups per CU)
-        const int tile_default = g.n_points >= 128LL * 256 ? 130 : 64;
-        const int rc3 = nsff_h3_field_query(desc, packed_v, args, g.tile_points ? g.tile_points : tile_default, st, span);
+        const int rc3 = nsff_h3_field_query(desc, packed_v, args, g.tile_points ? g.tile_points : nsff_h3_default_tile(g.n_points), st, span);
         if (rc3 != NSFF_OK) return rc3;
     } else {
         hipLaunchKernelGGL(nsff_field_kernel, dim3((unsigned)tiles), dim3(NTHREADS), 0, st, k);

@@ -2081,11 +2081,6 @@ static int h3_step_program(const NsffModelDesc& d, int static_mode, int transien
     return NSFF_OK;
 }
 
-// Host-only export of what a launch would execute (no GPU work): the step program and, when the hand-scheduled body covers the
-// launch's trunks, its phase programs -- tests pin h3a_build_program to the builder the simulator runs (tools/h3asm/check.py).
-// steps: [n][4] = {w_off (words), bias_off (words, NSFF_NONE = accumulate), nks | pre << 8 | post << 16 | head << 24, 0};
-// phases_static / phases_dynamic: [H3A_MAX_PHASES][8] descriptors; n_phases[2] = descriptors written (0 = trunk absent or
-// not covered).
 // The phase program of a PERSISTENT workgroup (tools/h3asm/check.py::make_persistent is the simulated reference): the last
 // segment's B phase B16L becomes B16LP with descriptor 0's stream fields -- behind its k-steps 1..8 it requests weight slots 0..7
 // of the trunk's first segments, which the workgroup's next tile finds resident (as a first tile finds what the pre-issue
@@ -2098,50 +2093,6 @@ static bool h3a_make_persistent(H3APhase* ph) {
     ph[at].d[0] = H3A_BODY_B16LP;
     for (int j = 3; j < 8; ++j) ph[at].d[j] = ph[0].d[j];
     return true;
-}
-
-extern "C" int nsff_field_phase_program(const NsffModelDesc* desc, int static_mode, int transient_mode, int fold_t, uint32_t* steps,
-                                int* n_steps, int* n_static_steps, uint32_t* phases_static, uint32_t* phases_dynamic, int* n_phases) {
-    if (!desc || !steps || !n_steps || !n_static_steps || !phases_static || !phases_dynamic || !n_phases) return NSFF_ERR_NULL;
-    H3KArgs k{};
-    int rc = nsff_make_layout_h3(*desc, k.L);
-    if (rc) return rc;
-    // fold_t bit 1: the launch is given NsffFieldArgs::s_bias (a view-direction static trunk with per-ray [dir | a] rows)
-    const bool side_fold = (fold_t & 2) != 0 && static_mode == 2 && desc->use_viewdir;
-    const bool persist = (fold_t & 4) != 0;       // bit 2: the programs of a persistent launch
-    fold_t &= 1;
-    rc = h3_step_program(*desc, static_mode, transient_mode, true, k, side_fold);
-    if (rc) return rc;
-    for (int i = 0; i < k.n_steps; ++i) {
-        const H3Step& st = k.steps[i];
-        steps[4 * i + 0] = st.w_off; steps[4 * i + 1] = st.bias_off;
-        steps[4 * i + 2] = (uint32_t)st.nks | ((uint32_t)st.pre << 8) | ((uint32_t)st.post << 16) | ((uint32_t)st.head << 24);
-        steps[4 * i + 3] = 0;
-    }
-    *n_steps = k.n_steps; *n_static_steps = k.n_static_steps;
-    n_phases[0] = n_phases[1] = 0;
-    H3APhase ph[H3A_MAX_PHASES];
-    uint32_t boff[H3A_MAX_BIAS];
-    int nb = 0, head = 0;
-    if (k.n_static_steps > 0 && (side_fold || !(static_mode == 2 && desc->use_viewdir))) {
-        for (auto& p : ph) for (auto& x : p.d) x = 0;
-        int np = 0;
-        k.sb_rows = side_fold ? 1 : 0;
-        if (h3a_build_program(k, 0, k.n_static_steps, false, false, ph, boff, nb, head, &np, side_fold) && (!persist || h3a_make_persistent(ph))) {
-            n_phases[0] = np;
-            for (int i = 0; i < n_phases[0]; ++i) for (int j = 0; j < 8; ++j) phases_static[8 * i + j] = ph[i].d[j];
-        }
-    }
-    if (k.n_steps > k.n_static_steps) {
-        for (auto& p : ph) for (auto& x : p.d) x = 0;
-        int np = 0;
-        k.tb_rows = fold_t ? nsff_time_bias_rows(desc) : 0;
-        if (h3a_build_program(k, k.n_static_steps, k.n_steps, true, fold_t != 0, ph, boff, nb, head, &np) && (!persist || h3a_make_persistent(ph))) {
-            n_phases[1] = np;
-            for (int i = 0; i < n_phases[1]; ++i) for (int j = 0; j < 8; ++j) phases_dynamic[8 * i + j] = ph[i].d[j];
-        }
-    }
-    return NSFF_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2388,18 +2339,19 @@ __global__ __launch_bounds__(256) void nsff_side_tile_kernel(const SideTileArgs 
 }
 }  // namespace
 
-int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const NsffFieldArgs* args,
-                        int points_per_block, hipStream_t st, unsigned long long* span) {
-    const NsffModelDesc& d = *desc;
-    const NsffFieldArgs& g = *args;
-    g_nsff_last_h3_grid = 0;
-    H3KArgs k{};
+// ---------------------------------------------------------------------------------------------------------------------
+// The dispatcher of the f16x3 field launches: fill (validate, marshal) -> plan (which kernels, grids and arguments: a pure
+// function, nsff_field_launch_plan shows it to CPU tests) -> issue (the launches).
+
+// validation + NsffFieldArgs -> H3KArgs (k arrives zeroed), and the launch's step program
+static int h3_fill_args(const NsffModelDesc& d, const NsffFieldArgs& g, const void* packed, unsigned long long* span, uint32_t* range,
+                        H3KArgs& k) {
     const int rc = nsff_make_layout_h3(d, k.L);
     if (rc) return rc;
     if (g.xyz && 3 + 6 * g.n_freqs != d.in_xyz) return NSFF_ERR_INVALID;
     k.packed = reinterpret_cast<const uint32_t*>(packed);
     k.span = span;
-    k.range = nsff_range_word(st);
+    k.range = range;
     k.xyz = g.xyz; k.x_emb = g.x_emb; k.dir_emb = g.dir_emb; k.a_emb = g.a_emb; k.t_emb = g.t_emb;
     k.raw = g.raw; k.n_points = g.n_points; k.pts_per_ray = g.pts_per_ray;
     k.save_acts = reinterpret_cast<_Float16*>(g.save_acts);
@@ -2410,11 +2362,9 @@ int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const Nsf
     k.save_stride = k.n_tiles * 64 * NSFF_W;
     if ((g.save_acts || g.save_xin || g.save_masks || g.save_side) && !g.xyz) return NSFF_ERR_INVALID;
     const void* const lo_of[3] = {g.save_acts, g.save_xin, g.save_side};
-    bool save_lo = false;
     for (int i = 0; i < 3; ++i) {
         if (g.save_lo_delta[i] < 0 || (g.save_lo_delta[i] & 7) || (g.save_lo_delta[i] != 0 && !lo_of[i])) return NSFF_ERR_INVALID;
         k.lo_delta[i] = g.save_lo_delta[i];
-        save_lo = save_lo || g.save_lo_delta[i] != 0;
     }
     k.xin_rows = (k.L.k0s + k.L.kt) <= 128 ? 128 : 256;          // row geometry of save_xin / save_side (nsff_train_dims)
     k.side_rows = k.L.side_k <= 128 ? 128 : 256;
@@ -2428,213 +2378,305 @@ int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const Nsf
     for (int i = 0; i + 1 < g.n_freqs; ++i)
         if (g.freqs[i + 1] != 2.0f * g.freqs[i]) k.octave_freqs = 0;
     k.ld_emb = g.ld_emb; k.off_xyz = g.off_xyz; k.off_dir = g.off_dir; k.off_a = g.off_a; k.off_t = g.off_t;
-
     // Every f16x3 launch -- inference and training forward alike -- runs the FOLDED step program: the activation-free
     // *_xyz_encoding_final layers are never executed, the heads that read them are evaluated with pre-multiplied rows.  A
     // training forward saves the trunk layers' activations only; the backward pass (field_bwd.hip) is folded the same way.
-    const bool fold = true;
-    {
-        const int prc = h3_step_program(d, g.static_mode, g.transient_mode, fold, k);
-        if (prc != NSFF_OK) return prc;
-    }
-    const int n = k.n_steps;
+    return h3_step_program(d, g.static_mode, g.transient_mode, true, k);
+}
 
+// What a launch issues, in order: at most nsff_side_tile_kernel, one compiler-scheduled launch, one hand-scheduled launch.
+struct H3Launch { int kernel; unsigned grid, block; };       // kernel: NSFF_LAUNCH_* -- its arguments are H3Plan::side / k / ka
+struct H3Plan {
+    int kernel;            // NSFF_KERNEL_* that nsff_last_field_kernel reports (0: none decided)
+    int grid;              // what nsff_last_field_grid reports
+    int n;
+    H3Launch launch[3];
+    SideTileArgs side;     // of NSFF_LAUNCH_SIDE_TILE
+    H3KArgs k;             // of the compiler-scheduled kernels (NSFF_LAUNCH_H3_*)
+    H3AArgs ka;            // of NSFF_LAUNCH_H3A / NSFF_LAUNCH_H3A_SAVE
+};
+
+// Per-ray bias rows (nsff_time_bias, nsff_side_bias) apply when no 64-point half straddles two rays.
+static bool h3a_ray_rows_apply(const NsffFieldArgs& g) {
+    return g.pts_per_ray > 0 && g.pts_per_ray % 64 == 0 && g.n_points <= 0x7fffffffLL;
+}
+
+// Does the hand-scheduled body read this launch's inputs (and, save: write its outputs)?  Raw positions, a 64-column position
+// embedding, time codes of at most 64 columns in aligned float4 rows; never with points_per_block == 131.
+static bool h3a_covers_inputs(bool save, int points_per_block, const H3KArgs& k, const NsffModelDesc& d, const NsffFieldArgs& g) {
+    if (points_per_block == 131 || g.xyz == nullptr || k.L.k0s != 64) return false;
+    if (g.transient_mode && !(k.L.kt == 64 && (d.in_t & 3) == 0 && ((uintptr_t)g.t_emb & 15) == 0)) return false;
+    if (!save) return true;
+    // Training forward only: activation and sign-word buffers both given, an EVEN number of 64-point tiles (a workgroup saves
+    // both of its tiles) below 4 GiB per slot, and no remainder planes for the three-product backward
+    // (NsffFieldArgs::save_lo_delta: the eight-wave kernel writes them).
+    const bool save_lo = k.lo_delta[0] != 0 || k.lo_delta[1] != 0 || k.lo_delta[2] != 0;
+    return !save_lo && k.save_acts != nullptr && k.save_masks != nullptr && (k.n_tiles & 1) == 0 &&
+           k.n_tiles * (64LL * NSFF_W * 2) < 0x100000000LL && g.n_points <= 0x7fffffffLL;
+}
+
+// A view-direction static trunk (the reference's documented training configuration, README.md:226-233) is covered when the caller
+// supplied its per-ray rows (nsff_side_bias) and they apply.  Training forward only: the [dir | a] tile the weight-gradient GEMM
+// reads (save_side) is then written from the per-ray codes by nsff_side_tile_kernel, so these must be there.
+static bool h3a_side_rows_given(bool save, const NsffModelDesc& d, const NsffFieldArgs& g) {
+    if (g.s_bias == nullptr || g.s_bias_rows != 1 || !h3a_ray_rows_apply(g)) return false;
+    return !save || (g.dir_emb != nullptr && (d.in_a == 0 || g.a_emb != nullptr));
+}
+
+static int h3a_phase_cost(const H3APhase* ph) {       // matrix steps of a trunk's phase program
+    int c = 0;
+    for (int i = 1; i < H3A_MAX_PHASES && !(i > 1 && ph[i].d[0] == H3A_BODY_END); ++i) {
+        const uint32_t b = ph[i].d[0];
+        c += (b == H3A_BODY_A16R || b == H3A_BODY_A16RS) ? 16 : ((b == H3A_BODY_A4 || b == H3A_BODY_A4F) ? 4 : ((b == H3A_BODY_A8 || b == H3A_BODY_A8F) ? 8 : 0));
+    }
+    return c;
+}
+
+// Persistent form (H3AArgs::p_mode): one workgroup per CU walking its tiles -- for launches that give every workgroup at
+// least one tile.  Each workgroup keeps ONE trunk: trunks of equal cost split the chip by XCD, unequal ones (the
+// view-direction static trunk is 23 % longer than the dynamic one) by their share of the matrix steps.
+// trunks: 1 = one trunk in the launch, 2 = both, 3 = the dynamic trunk of a launch whose static trunk is another kernel's.
+// Patches ka's phase programs and p_* fields; returns the grid (one workgroup per tile and trunk when the form does not apply).
+static unsigned h3a_plan_persistent(H3AArgs& ka, long long tiles, int n_cus, bool no_persist, int trunks) {
+    unsigned grid = (unsigned)(trunks == 2 ? 2 * tiles : tiles);
+    if (no_persist || n_cus < 8 || n_cus % 8 != 0) return grid;
+    if (trunks == 3) {
+        if (tiles >= n_cus && h3a_make_persistent(ka.ph[1])) { ka.p_mode = 3; ka.p_tiles = tiles; grid = (unsigned)n_cus; }
+    } else if (trunks == 1) {
+        if (tiles >= n_cus && h3a_make_persistent(ka.ph[ka.k.n_static_steps > 0 ? 0 : 1])) { ka.p_mode = 1; ka.p_tiles = tiles; grid = (unsigned)n_cus; }
+    } else if (tiles >= n_cus / 2) {
+        const int cs = h3a_phase_cost(ka.ph[0]), cd = h3a_phase_cost(ka.ph[1]);
+        const bool equal = 25 * std::abs(cs - cd) <= std::max(cs, cd);
+        // Unequal trunks (mode 4, see H3AArgs): the longer trunk (cost cl per tile) hands its last `steal` tiles to the
+        // second round, run by the shorter trunk's XCDs behind their own tiles:  (tiles - steal) cl = tiles cs' + steal cl
+        const int cl = std::max(cs, cd), csh = std::min(cs, cd);
+        const long long steal = equal ? 0 : (tiles * (cl - csh) + cl) / (2LL * cl);
+        H3APhase keep[H3A_MAX_PHASES];
+        for (int i = 0; i < H3A_MAX_PHASES; ++i) keep[i] = ka.ph[0][i];
+        if (tiles - steal >= n_cus / 2 && h3a_make_persistent(ka.ph[0])) {       // (every first-round workgroup needs a tile)
+            if (h3a_make_persistent(ka.ph[1])) {
+                ka.p_tiles = tiles; grid = (unsigned)n_cus;
+                if (steal == 0) ka.p_mode = 2;
+                else { ka.p_mode = 4; ka.p_long = cs > cd ? 0 : 1; ka.p_split = (int)(tiles - steal); grid = 2u * (unsigned)n_cus; }
+            } else for (int i = 0; i < H3A_MAX_PHASES; ++i) ka.ph[0][i] = keep[i];
+        }
+    }
+    return grid;
+}
+
+// The plan of one launch: no HIP call, no environment, no global.  p arrives zeroed; k is h3_fill_args' result.
+// points_per_block 64: the 64-point tiling.  130 / 131: 128 points per workgroup -- the hand-scheduled body (nsff_field_kernel_h3a,
+// training forward: nsff_field_kernel_h3a_save) whenever it covers the launch, otherwise -- and always with 131 -- eight waves of
+// 32 neurons, compiler-scheduled (half the weight stream of the 64-point tiling).
+static int h3_plan_launch(const NsffModelDesc& d, const H3KArgs& k, const NsffFieldArgs& g, int points_per_block, int n_cus,
+                          bool no_persist, H3Plan& p) {
+    const bool saves = k.save_acts || k.save_xin || k.save_masks || k.save_side;      // training forward
     // one trunk per workgroup when the launch evaluates both (see the kernel): grid = 2 x tiles
-    const bool both = n > k.n_static_steps && k.n_static_steps > 0;
-    auto launch = [&](auto kernel, int tile_points, int threads) -> int {
+    const bool both = k.n_steps > k.n_static_steps && k.n_static_steps > 0;
+    auto compiler_scheduled = [&](int launch_kernel, int tile_points, unsigned threads) -> int {
+        p.kernel = saves ? NSFF_KERNEL_H3_SAVE : (tile_points == 64 ? NSFF_KERNEL_H3_64 : NSFF_KERNEL_H3_8WAVE);
         const long long tiles = (g.n_points + tile_points - 1) / tile_points;
         if (tiles * 2 > 0x7fffffffLL) return NSFF_ERR_INVALID;
-        k.grid_tiles = tiles;
-        k.split_trunks = both ? 1 : 0;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(both ? 2 * tiles : tiles)), dim3(threads), 0, st, k);
+        p.k = k;
+        p.k.grid_tiles = tiles;
+        p.k.split_trunks = both ? 1 : 0;
+        p.launch[p.n++] = H3Launch{launch_kernel, (unsigned)(both ? 2 * tiles : tiles), threads};
         return NSFF_OK;
     };
-    int lrc;
-    const bool saves = k.save_acts || k.save_xin || k.save_masks || k.save_side;
-    if (saves && points_per_block == 64) { // training forward, 64-point tiling (A/B against the default below)
-        lrc = launch(nsff_field_kernel_h3<2, 1, true>, 64, 256);
-        g_nsff_last_h3_kernel = NSFF_KERNEL_H3_SAVE;
-    } else if (saves) {
-        // Training forward, 128-point tiles.  Default: the hand-scheduled body in its SAVE build (nsff_field_kernel_h3a_save) for
-        // launches it covers -- raw positions, a 64-column position embedding, time codes of at most 64 columns in float4 rows,
-        // no view-direction branch (its [dir | a] input tile is the eight-wave kernel's), activation and sign-word buffers both
-        // given, an EVEN number of 64-point tiles (a workgroup saves both of its tiles) below 4 GiB per slot; otherwise -- and with
-        // points_per_block == 131 -- eight waves of 32 neurons, compiler-scheduled.
-        H3AArgs ka{};
-        ka.n_bias[0] = ka.n_bias[1] = 0; ka.head[0] = ka.head[1] = HEAD_NONE;
-        // A view-direction static trunk (round 6; the reference's documented training configuration, README.md:226-233): covered when
-        // the caller supplied its per-ray rows (nsff_side_bias) and no 64-point half straddles two rays -- the launch then runs the
-        // side-fold step program of the inference launches (static_dir_encoding as one folded 256-wide segment with per-ray bias
-        // rows, sigma as a ride of the last trunk layer's epilogues) in its SAVE build; the [dir | a] input tile the weight-gradient
-        // GEMM of those columns reads (save_side) is written by a small launch of its own from the per-ray rows.
-        const bool viewdir_static = g.static_mode == 2 && d.use_viewdir;
-        H3KArgs ks = k;
-        bool side = false;
-        // (remainder planes for the three-product backward, NsffFieldArgs::save_lo_delta: the eight-wave kernel writes them)
-        bool asm_body = points_per_block != 131 && !save_lo && g.xyz != nullptr && k.L.k0s == 64 &&
-                        k.save_acts != nullptr && k.save_masks != nullptr && (k.n_tiles & 1) == 0 &&
-                        k.n_tiles * (64LL * NSFF_W * 2) < 0x100000000LL && g.n_points <= 0x7fffffffLL;
-        if (asm_body && viewdir_static)
-            asm_body = g.s_bias != nullptr && g.s_bias_rows == 1 && g.pts_per_ray > 0 && g.pts_per_ray % 64 == 0 && g.dir_emb != nullptr &&
-                       (d.in_a == 0 || g.a_emb != nullptr) && h3_step_program(d, g.static_mode, g.transient_mode, true, ks, true) == NSFF_OK;
-        else if (asm_body)
-            asm_body = k.save_side == nullptr;
-        if (asm_body && g.transient_mode)
-            asm_body = k.L.kt == 64 && (d.in_t & 3) == 0 && ((uintptr_t)g.t_emb & 15) == 0;
-        if (asm_body) {
-            if (viewdir_static) { ks.s_bias = g.s_bias; ks.sb_rows = 1; side = true; }
-            ka.k = ks;
-            if (ks.n_static_steps > 0)
-                asm_body = h3a_build_program(ks, 0, ks.n_static_steps, false, false, ka.ph[0], ka.bias_off[0], ka.n_bias[0], ka.head[0],
-                                             nullptr, side, side ? &ka.sig_ride : nullptr, true);
-            if (asm_body && ks.n_steps > ks.n_static_steps)
-                asm_body = h3a_build_program(ks, ks.n_static_steps, ks.n_steps, true, false, ka.ph[1], ka.bias_off[1], ka.n_bias[1], ka.head[1],
-                                             nullptr, false, nullptr, true);
-        }
-        if (asm_body) {
-            const long long tiles = (g.n_points + 127) / 128;
-            if (tiles * 2 > 0x7fffffffLL) return NSFF_ERR_INVALID;
-            if (side) {
-                ka.sig_b_off = k.L.s_sigma_b;
-                if (k.save_side != nullptr) {
-                    SideTileArgs sa{g.dir_emb, g.a_emb, k.save_side, g.n_points, g.pts_per_ray, d.in_dir, d.in_a, k.side_rows, k.range};
-                    hipLaunchKernelGGL(nsff_side_tile_kernel, dim3((unsigned)k.n_tiles), dim3(256), 0, st, sa);
-                }
-            }
-            ka.hsel[0] = h3a_head_sel(k.L, ka.head[0]); ka.hsel[1] = h3a_head_sel(k.L, ka.head[1]);
-            ka.k.grid_tiles = tiles;
-            ka.k.split_trunks = both ? 1 : 0;
-            hipLaunchKernelGGL(nsff_field_kernel_h3a_save, dim3((unsigned)(both ? 2 * tiles : tiles)), dim3(256), 0, st, ka);
-            lrc = NSFF_OK;
-            g_nsff_last_h3_kernel = NSFF_KERNEL_H3A_SAVE;
-        } else {                                  // eight waves of 32 neurons
-            lrc = launch(nsff_field_kernel_h3<4, 1, true, 1>, 128, 512);
-            g_nsff_last_h3_kernel = NSFF_KERNEL_H3_SAVE;
-        }
-    } else if (points_per_block == 64) {
-        lrc = launch(nsff_field_kernel_h3<2, 1>, 64, 256);
-        g_nsff_last_h3_kernel = NSFF_KERNEL_H3_64;
-    } else {
-        // 128 points per workgroup.  Default: the hand-scheduled body (nsff_field_kernel_h3a) whenever the launch's trunks have a
-        // structure it executes (raw positions, a 64-column position embedding, a time code of at most 64 columns in float4
-        // rows, no view-direction branch in this launch); otherwise -- and with points_per_block == 131 -- the
-        // compiler-scheduled eight-wave form.
-        // A launch whose STATIC trunk has the view-direction branch (not covered) next to a dynamic trunk is issued as two
-        // launches: the static workgroups on the eight-wave kernel, the dynamic ones on the hand-scheduled kernel -- each
-        // writes its own part of the raw records (piece 1 / piece 2), as the workgroups of one split launch do.
-        bool static_uncovered = g.static_mode == 2 && d.use_viewdir;
-        H3AArgs ka{};
-        ka.n_bias[0] = ka.n_bias[1] = 0; ka.head[0] = ka.head[1] = HEAD_NONE;
-        const bool asm_inputs = points_per_block != 131 && g.xyz != nullptr && k.L.k0s == 64;
-        // A view-direction static trunk is covered when the caller supplied its per-ray rows (nsff_side_bias) and no 64-point half
-        // straddles two rays: the launch then runs the side-fold step program (static_dir_encoding as one folded 256-wide segment
-        // with per-ray bias rows, sigma as a ride of the last trunk layer's epilogues) -- `ks` replaces `k` for this launch.
-        H3KArgs ks = k;
-        bool side = false;
-        if (static_uncovered && asm_inputs && g.s_bias != nullptr && g.s_bias_rows == 1 && g.pts_per_ray > 0 &&
-            g.pts_per_ray % 64 == 0 && g.n_points <= 0x7fffffffLL &&
-            h3_step_program(d, g.static_mode, g.transient_mode, true, ks, true) == NSFF_OK) {
+    if (points_per_block == 64) return compiler_scheduled(saves ? NSFF_LAUNCH_H3_64_SAVE : NSFF_LAUNCH_H3_64, 64, 256);
+
+    H3AArgs& ka = p.ka;
+    ka.head[0] = ka.head[1] = HEAD_NONE;
+    bool covered = h3a_covers_inputs(saves, points_per_block, k, d, g);
+    // With its per-ray rows a view-direction static trunk runs the side-fold step program (static_dir_encoding as one folded
+    // 256-wide segment with per-ray bias rows, sigma as a ride of the last trunk layer's epilogues) -- `ks` replaces `k` then.
+    const bool viewdir_static = g.static_mode == 2 && d.use_viewdir;
+    H3KArgs ks = k;
+    bool side = false;
+    if (covered && viewdir_static) {
+        side = h3a_side_rows_given(saves, d, g) && h3_step_program(d, g.static_mode, g.transient_mode, true, ks, true) == NSFF_OK;
+        if (side) {
             ks.s_bias = g.s_bias; ks.sb_rows = 1;
             side = h3a_build_program(ks, 0, ks.n_static_steps, false, false, ka.ph[0], ka.bias_off[0], ka.n_bias[0], ka.head[0], nullptr,
-                                     true, &ka.sig_ride);
+                                     true, &ka.sig_ride, saves);
         }
-        if (side) { static_uncovered = false; ka.sig_b_off = k.L.s_sigma_b; }
+        if (side) ka.sig_b_off = k.L.s_sigma_b;
         else { ks = k; ka.sig_ride = 0; ka.n_bias[0] = 0; ka.head[0] = HEAD_NONE; }
-        const int ns = ks.n_steps;
-        bool asm_body = asm_inputs && !(static_uncovered && !g.transient_mode);
-        if (asm_body && g.transient_mode)
-            asm_body = k.L.kt == 64 && (d.in_t & 3) == 0 && ((uintptr_t)g.t_emb & 15) == 0;
-        if (asm_body) {
-            ka.k = ks;
-            if (ks.n_static_steps > 0 && !static_uncovered && !side)
-                asm_body = h3a_build_program(ks, 0, ks.n_static_steps, false, false, ka.ph[0], ka.bias_off[0], ka.n_bias[0], ka.head[0]);
-            if (asm_body && ns > ks.n_static_steps) {
-                // the time code as per-ray bias rows (nsff_time_bias): whenever the caller supplied them and a 64-point half
-                // never straddles two rays; otherwise the body multiplies the time-code columns like any other input
-                bool fold_t = g.t_bias != nullptr && g.pts_per_ray > 0 && g.pts_per_ray % 64 == 0 && g.n_points <= 0x7fffffffLL &&
-                              g.t_bias_rows == nsff_time_bias_rows(desc);
-                if (fold_t) {
-                    ka.k.t_bias = g.t_bias; ka.k.tb_rows = g.t_bias_rows;
-                    fold_t = h3a_build_program(ka.k, ks.n_static_steps, ns, true, true, ka.ph[1], ka.bias_off[1], ka.n_bias[1], ka.head[1]);
-                }
-                if (!fold_t) {
-                    ka.k.t_bias = nullptr; ka.k.tb_rows = 0;
-                    asm_body = h3a_build_program(ks, ks.n_static_steps, ns, true, false, ka.ph[1], ka.bias_off[1], ka.n_bias[1], ka.head[1]);
-                }
+    }
+    const bool static_uncovered = viewdir_static && !side;
+    // Inference: an uncovered view-direction static trunk NEXT TO a dynamic trunk is issued as two launches -- the static
+    // workgroups on the eight-wave kernel, the dynamic ones on the hand-scheduled kernel; each writes its own part of the raw
+    // records (piece 1 / piece 2), as the workgroups of one split launch do.  A training forward has no such split, and without
+    // the view-direction branch its [dir | a] input tile (save_side) is the eight-wave kernel's.
+    const bool two_launches = !saves && static_uncovered && g.transient_mode;
+    if (static_uncovered && !two_launches) covered = false;
+    if (saves && !viewdir_static && k.save_side != nullptr) covered = false;
+    if (covered) {
+        ka.k = ks;
+        if (ks.n_static_steps > 0 && !viewdir_static)
+            covered = h3a_build_program(ks, 0, ks.n_static_steps, false, false, ka.ph[0], ka.bias_off[0], ka.n_bias[0], ka.head[0], nullptr,
+                                        false, nullptr, saves);
+        if (covered && ks.n_steps > ks.n_static_steps) {
+            // Inference only: the time code as per-ray bias rows (nsff_time_bias) whenever the caller supplied them and they
+            // apply; otherwise the body multiplies the time-code columns like any other input (a training forward always does:
+            // those columns' weight gradients need the saved tile)
+            bool fold_t = !saves && g.t_bias != nullptr && h3a_ray_rows_apply(g) && g.t_bias_rows == nsff_time_bias_rows(&d);
+            if (fold_t) {
+                ka.k.t_bias = g.t_bias; ka.k.tb_rows = g.t_bias_rows;
+                fold_t = h3a_build_program(ka.k, ks.n_static_steps, ks.n_steps, true, true, ka.ph[1], ka.bias_off[1], ka.n_bias[1], ka.head[1]);
             }
-        }
-        if (side && !asm_body) {
-            // (the dynamic trunk of this launch is not covered: back to the plain step program, static trunk on the eight-wave kernel)
-            static_uncovered = true; side = false;
-            asm_body = false;
-        }
-        const long long tiles = (g.n_points + 127) / 128;
-        if (tiles * 2 > 0x7fffffffLL) return NSFF_ERR_INVALID;
-        ka.hsel[0] = h3a_head_sel(k.L, ka.head[0]); ka.hsel[1] = h3a_head_sel(k.L, ka.head[1]);
-        const int which = side ? NSFF_KERNEL_H3A_SIDE : (ka.k.t_bias ? NSFF_KERNEL_H3A_TBIAS : NSFF_KERNEL_H3A);
-        // Persistent form (H3AArgs::p_mode): one workgroup per CU walking its tiles -- for launches that give every workgroup at
-        // least one tile.  Each workgroup keeps ONE trunk: trunks of equal cost split the chip by XCD, unequal ones (the
-        // view-direction static trunk is 23 % longer than the dynamic one) by their share of the matrix steps.
-        // NSFF_NO_PERSIST=1: one workgroup per tile (A/B).
-        const int n_cus = h3a_device_cus();
-        const bool no_persist = g.launch_form == 1 || getenv("NSFF_NO_PERSIST") != nullptr;       // (the variable is read per launch: tests flip it)
-        const bool can_persist = !no_persist && n_cus >= 8 && n_cus % 8 == 0;
-        auto cost = [&](const H3APhase* ph) {
-            int c = 0;
-            for (int i = 1; i < H3A_MAX_PHASES && !(i > 1 && ph[i].d[0] == H3A_BODY_END); ++i) {
-                const uint32_t b = ph[i].d[0];
-                c += (b == H3A_BODY_A16R || b == H3A_BODY_A16RS) ? 16 : ((b == H3A_BODY_A4 || b == H3A_BODY_A4F) ? 4 : ((b == H3A_BODY_A8 || b == H3A_BODY_A8F) ? 8 : 0));
+            if (!fold_t) {
+                ka.k.t_bias = nullptr; ka.k.tb_rows = 0;
+                covered = h3a_build_program(ks, ks.n_static_steps, ks.n_steps, true, false, ka.ph[1], ka.bias_off[1], ka.n_bias[1], ka.head[1],
+                                            nullptr, false, nullptr, saves);
             }
-            return c;
-        };
-        if (asm_body && static_uncovered) {
-            // (1) static trunk: the first half of a split launch's grid = static workgroups only
-            k.grid_tiles = tiles;
-            k.split_trunks = 1;
-            hipLaunchKernelGGL((nsff_field_kernel_h3<4, 1, false, 1>), dim3((unsigned)tiles), dim3(512), 0, st, k);
-            // (2) dynamic trunk: a split launch whose static half is empty (grid_tiles = 0: every workgroup is a dynamic one)
-            ka.k.grid_tiles = 0;
-            ka.k.split_trunks = 1;
-            unsigned grid = (unsigned)tiles;
-            if (can_persist && tiles >= n_cus && h3a_make_persistent(ka.ph[1])) { ka.p_mode = 3; ka.p_tiles = tiles; grid = (unsigned)n_cus; }
-            hipLaunchKernelGGL(nsff_field_kernel_h3a, dim3(grid), dim3(256), 0, st, ka);
-            lrc = NSFF_OK;
-            g_nsff_last_h3_kernel = which;
-            g_nsff_last_h3_grid = (int)grid;
-        } else if (asm_body) {
-            const bool both2 = ns > ks.n_static_steps && ks.n_static_steps > 0;
-            ka.k.grid_tiles = tiles;
-            ka.k.split_trunks = both2 ? 1 : 0;
-            unsigned grid = (unsigned)(both2 ? 2 * tiles : tiles);
-            if (can_persist && !both2 && tiles >= n_cus && h3a_make_persistent(ka.ph[ks.n_static_steps > 0 ? 0 : 1])) {
-                ka.p_mode = 1; ka.p_tiles = tiles; grid = (unsigned)n_cus;
-            }
-            if (can_persist && both2 && tiles >= n_cus / 2) {
-                const int cs = cost(ka.ph[0]), cd = cost(ka.ph[1]);
-                const bool equal = 25 * std::abs(cs - cd) <= std::max(cs, cd);
-                // Unequal trunks (mode 4, see H3AArgs): the longer trunk (cost cl per tile) hands its last `steal` tiles to the
-                // second round, run by the shorter trunk's XCDs behind their own tiles:  (tiles - steal) cl = tiles cs' + steal cl
-                const int cl = std::max(cs, cd), csh = std::min(cs, cd);
-                const long long steal = equal ? 0 : (tiles * (cl - csh) + cl) / (2LL * cl);
-                H3APhase keep[H3A_MAX_PHASES];
-                for (int i = 0; i < H3A_MAX_PHASES; ++i) keep[i] = ka.ph[0][i];
-                if (tiles - steal >= n_cus / 2 && h3a_make_persistent(ka.ph[0])) {       // (every first-round workgroup needs a tile)
-                    if (h3a_make_persistent(ka.ph[1])) {
-                        ka.p_tiles = tiles; grid = (unsigned)n_cus;
-                        if (steal == 0) ka.p_mode = 2;
-                        else { ka.p_mode = 4; ka.p_long = cs > cd ? 0 : 1; ka.p_split = (int)(tiles - steal); grid = 2u * (unsigned)n_cus; }
-                    } else for (int i = 0; i < H3A_MAX_PHASES; ++i) ka.ph[0][i] = keep[i];
-                }
-            }
-            hipLaunchKernelGGL(nsff_field_kernel_h3a, dim3(grid), dim3(256), 0, st, ka);
-            lrc = NSFF_OK;
-            g_nsff_last_h3_kernel = which;
-            g_nsff_last_h3_grid = (int)grid;
-        } else {                                  // eight waves of 32 neurons (half the weight stream of the 64-point tiling)
-            lrc = launch(nsff_field_kernel_h3<4, 1, false, 1>, 128, 512);
-            g_nsff_last_h3_kernel = NSFF_KERNEL_H3_8WAVE;
         }
     }
-    if (lrc != NSFF_OK) return lrc;
+    const long long tiles = (g.n_points + 127) / 128;
+    // (an inference launch checks its grid before it settles on a kernel, a training forward on the kernel's own path)
+    if ((covered || !saves) && tiles * 2 > 0x7fffffffLL) return NSFF_ERR_INVALID;
+    // (not covered -- also: the side-fold program's dynamic partner is not -- the plain step program on the eight-wave kernel)
+    if (!covered) return compiler_scheduled(saves ? NSFF_LAUNCH_H3_8WAVE_SAVE : NSFF_LAUNCH_H3_8WAVE, 128, 512);
+    ka.hsel[0] = h3a_head_sel(k.L, ka.head[0]); ka.hsel[1] = h3a_head_sel(k.L, ka.head[1]);
+    if (saves) {
+        if (side && k.save_side != nullptr) {
+            p.side = SideTileArgs{g.dir_emb, g.a_emb, k.save_side, g.n_points, g.pts_per_ray, d.in_dir, d.in_a, k.side_rows, k.range};
+            p.launch[p.n++] = H3Launch{NSFF_LAUNCH_SIDE_TILE, (unsigned)k.n_tiles, 256};
+        }
+        ka.k.grid_tiles = tiles;
+        ka.k.split_trunks = both ? 1 : 0;
+        p.launch[p.n++] = H3Launch{NSFF_LAUNCH_H3A_SAVE, (unsigned)(both ? 2 * tiles : tiles), 256};
+        p.kernel = NSFF_KERNEL_H3A_SAVE;
+        return NSFF_OK;
+    }
+    no_persist = no_persist || g.launch_form == 1;
+    unsigned grid;
+    if (two_launches) {
+        // (1) static trunk: the first half of a split launch's grid = static workgroups only
+        p.k = k;
+        p.k.grid_tiles = tiles;
+        p.k.split_trunks = 1;
+        p.launch[p.n++] = H3Launch{NSFF_LAUNCH_H3_8WAVE, (unsigned)tiles, 512};
+        // (2) dynamic trunk: a split launch whose static half is empty (grid_tiles = 0: every workgroup is a dynamic one)
+        ka.k.grid_tiles = 0;
+        ka.k.split_trunks = 1;
+        grid = h3a_plan_persistent(ka, tiles, n_cus, no_persist, 3);
+    } else {
+        ka.k.grid_tiles = tiles;
+        ka.k.split_trunks = both ? 1 : 0;
+        grid = h3a_plan_persistent(ka, tiles, n_cus, no_persist, both ? 2 : 1);
+    }
+    p.launch[p.n++] = H3Launch{NSFF_LAUNCH_H3A, grid, 256};
+    p.kernel = side ? NSFF_KERNEL_H3A_SIDE : (ka.k.t_bias ? NSFF_KERNEL_H3A_TBIAS : NSFF_KERNEL_H3A);
+    p.grid = (int)grid;
+    return NSFF_OK;
+}
+
+int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const NsffFieldArgs* args,
+                        int points_per_block, hipStream_t st, unsigned long long* span) {
+    H3KArgs k{};
+    H3Plan p{};
+    int rc = h3_fill_args(*desc, *args, packed, span, nsff_range_word(st), k);
+    // NSFF_NO_PERSIST=1: one workgroup per tile (A/B; the variable is read per launch: tests flip it)
+    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k, *args, points_per_block, h3a_device_cus(), getenv("NSFF_NO_PERSIST") != nullptr, p);
+    g_nsff_last_h3_grid = p.grid;
+    if (p.kernel) g_nsff_last_h3_kernel = p.kernel;
+    if (rc != NSFF_OK) return rc;
+    for (int i = 0; i < p.n; ++i) {
+        const dim3 grid(p.launch[i].grid), block(p.launch[i].block);
+        switch (p.launch[i].kernel) {              // (the templates in the order they have always been instantiated: same device binary)
+        case NSFF_LAUNCH_SIDE_TILE:     hipLaunchKernelGGL(nsff_side_tile_kernel, grid, block, 0, st, p.side); break;
+        case NSFF_LAUNCH_H3_64_SAVE:    hipLaunchKernelGGL((nsff_field_kernel_h3<2, 1, true>), grid, block, 0, st, p.k); break;
+        case NSFF_LAUNCH_H3_8WAVE_SAVE: hipLaunchKernelGGL((nsff_field_kernel_h3<4, 1, true, 1>), grid, block, 0, st, p.k); break;
+        case NSFF_LAUNCH_H3_64:         hipLaunchKernelGGL((nsff_field_kernel_h3<2, 1>), grid, block, 0, st, p.k); break;
+        case NSFF_LAUNCH_H3_8WAVE:      hipLaunchKernelGGL((nsff_field_kernel_h3<4, 1, false, 1>), grid, block, 0, st, p.k); break;
+        case NSFF_LAUNCH_H3A:           hipLaunchKernelGGL(nsff_field_kernel_h3a, grid, block, 0, st, p.ka); break;
+        case NSFF_LAUNCH_H3A_SAVE:      hipLaunchKernelGGL(nsff_field_kernel_h3a_save, grid, block, 0, st, p.ka); break;
+        }
+    }
     return nsff_launch_status();
+}
+
+static uint32_t nsff_plan_hash(const void* bytes, size_t n) {       // FNV-1a over a kernel's argument bytes
+    uint32_t h = 2166136261u;
+    for (size_t i = 0; i < n; ++i) h = (h ^ reinterpret_cast<const unsigned char*>(bytes)[i]) * 16777619u;
+    return h;
+}
+
+// Host-only view of the plan (include/nsff_render.h): no GPU work, no pointer of `args` is dereferenced.
+extern "C" int nsff_field_launch_plan(const NsffModelDesc* desc, const NsffFieldArgs* args, int32_t n_cus, int32_t no_persist,
+                                      int32_t* out, int32_t max_launches) {
+    if (!desc || !args || !out) return NSFF_ERR_NULL;
+    if (max_launches < 3) return NSFF_ERR_INVALID;
+    for (int i = 0; i < max_launches * NSFF_PLAN_WORDS; ++i) out[i] = 0;
+    if (args->precision == NSFF_PREC_F32) return NSFF_KERNEL_F32;          // (one kernel, one workgroup per 64-point tile)
+    const int tp = args->tile_points;
+    if (tp != 0 && tp != 64 && tp != 130 && tp != 131) return NSFF_ERR_INVALID;
+    H3KArgs k{};
+    H3Plan p{};
+    int rc = h3_fill_args(*desc, *args, nullptr, nullptr, nullptr, k);
+    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k, *args, tp ? tp : nsff_h3_default_tile(args->n_points), n_cus, no_persist != 0, p);
+    if (rc != NSFF_OK) return rc;
+    for (int i = 0; i < p.n; ++i) {
+        int32_t* o = out + i * NSFF_PLAN_WORDS;
+        const int kn = p.launch[i].kernel;
+        o[0] = kn; o[1] = (int32_t)p.launch[i].grid; o[2] = (int32_t)p.launch[i].block;
+        if (kn == NSFF_LAUNCH_SIDE_TILE) { o[11] = (int32_t)nsff_plan_hash(&p.side, sizeof p.side); continue; }
+        const bool a = kn == NSFF_LAUNCH_H3A || kn == NSFF_LAUNCH_H3A_SAVE;
+        const H3KArgs& lk = a ? p.ka.k : p.k;
+        if (a) { o[3] = p.ka.p_mode; o[4] = (int32_t)p.ka.p_tiles; o[5] = p.ka.p_split; o[6] = p.ka.p_long; }
+        o[7] = lk.split_trunks; o[8] = (int32_t)lk.grid_tiles; o[9] = lk.tb_rows; o[10] = lk.sb_rows;
+        o[11] = (int32_t)(a ? nsff_plan_hash(&p.ka, sizeof p.ka) : nsff_plan_hash(&p.k, sizeof p.k));
+    }
+    return p.kernel;
+}
+
+// Host-only export of what a launch would execute (no GPU work): the step program and, when the hand-scheduled body covers the
+// launch's trunks, its phase programs -- tests pin h3a_build_program to the builder the simulator runs (tools/h3asm/check.py).
+// steps: [n][4] = {w_off (words), bias_off (words, NSFF_NONE = accumulate), nks | pre << 8 | post << 16 | head << 24, 0};
+// phases_static / phases_dynamic: [H3A_MAX_PHASES][8] descriptors; n_phases[2] = descriptors written (0 = trunk absent or
+// not covered).  The answer is h3_plan_launch's, for an inference launch of raw positions in 128-point tiles whose rays hold 64
+// points each: with the per-ray rows the fold_t bits name, one workgroup per tile; bit 2 then patches each covered trunk's program
+// as a persistent launch does.
+extern "C" int nsff_field_phase_program(const NsffModelDesc* desc, int static_mode, int transient_mode, int fold_t, uint32_t* steps,
+                                int* n_steps, int* n_static_steps, uint32_t* phases_static, uint32_t* phases_dynamic, int* n_phases) {
+    if (!desc || !steps || !n_steps || !n_static_steps || !phases_static || !phases_dynamic || !n_phases) return NSFF_ERR_NULL;
+    NsffFieldArgs g{};
+    const float* const given = reinterpret_cast<const float*>(uintptr_t(64));      // (pointers are only tested, never read)
+    g.n_points = 128; g.precision = NSFF_PREC_F16X3; g.pts_per_ray = 64;
+    g.static_mode = static_mode; g.transient_mode = transient_mode;
+    g.xyz = g.dir_emb = g.a_emb = g.t_emb = given;
+    g.n_freqs = (desc->in_xyz - 3) / 6;
+    g.launch_form = 1;
+    // fold_t bit 0: the launch is given NsffFieldArgs::t_bias; bit 1: NsffFieldArgs::s_bias (a view-direction static trunk with
+    // per-ray [dir | a] rows); bit 2: the programs of a persistent launch
+    if (fold_t & 1) { g.t_bias = given; g.t_bias_rows = nsff_time_bias_rows(desc); }
+    if (fold_t & 2) { g.s_bias = given; g.s_bias_rows = 1; }
+    const bool persist = (fold_t & 4) != 0;
+    H3KArgs k0{};
+    H3Plan p{};
+    int rc = h3_fill_args(*desc, g, nullptr, nullptr, nullptr, k0);
+    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k0, g, 130, 0, true, p);
+    if (rc) return rc;
+    const bool body = p.launch[p.n - 1].kernel == NSFF_LAUNCH_H3A;
+    const H3KArgs& k = body ? p.ka.k : p.k;
+    for (int i = 0; i < k.n_steps; ++i) {
+        const H3Step& st = k.steps[i];
+        steps[4 * i + 0] = st.w_off; steps[4 * i + 1] = st.bias_off;
+        steps[4 * i + 2] = (uint32_t)st.nks | ((uint32_t)st.pre << 8) | ((uint32_t)st.post << 16) | ((uint32_t)st.head << 24);
+        steps[4 * i + 3] = 0;
+    }
+    *n_steps = k.n_steps; *n_static_steps = k.n_static_steps;
+    n_phases[0] = n_phases[1] = 0;
+    const bool has[2] = {k.n_static_steps > 0 && p.n == 1, k.n_steps > k.n_static_steps};      // (p.n == 2: the static trunk is the eight-wave kernel's)
+    uint32_t* const dst[2] = {phases_static, phases_dynamic};
+    for (int t = 0; t < 2 && body; ++t) {
+        H3APhase* ph = p.ka.ph[t];
+        if (!has[t] || (persist && !h3a_make_persistent(ph))) continue;
+        int np = 2;
+        while (ph[np].d[0] != H3A_BODY_END) ++np;
+        n_phases[t] = np + 2;                                  // (a program ends with two END descriptors)
+        for (int i = 0; i < n_phases[t]; ++i) for (int j = 0; j < 8; ++j) dst[t][8 * i + j] = ph[i].d[j];
+    }
+    return NSFF_OK;
 }

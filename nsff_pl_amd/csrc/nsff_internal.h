@@ -16,5 +16,10 @@ int nsff_fold_rows_f32(const NsffModelDesc* desc, const float* const* params, fl
 int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const NsffFieldArgs* args,
                         int points_per_block, hipStream_t st, unsigned long long* span = nullptr);
 
+// the library's choice of points_per_block (NsffFieldArgs::tile_points = 0): 128 points as eight waves of 32 neurons (one
+// workgroup per CU, every weight byte fetched once per 128 points, no spilled registers: 41 MB instead of 79 MB of HBM traffic
+// per C2 launch and -0.8 % time); launches too small to give every CU such a tile keep the 64-point tiling (two workgroups per CU)
+inline int nsff_h3_default_tile(long long n_points) { return n_points >= 128LL * 256 ? 130 : 64; }
+
 extern int g_nsff_last_h3_kernel;
 extern int g_nsff_last_h3_grid;
