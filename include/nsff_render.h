@@ -456,7 +456,8 @@ int nsff_adam_step_segments(float* param, const float* grad, float* exp_avg, flo
  * ray, or for the two flow terms the M rays whose projection is valid -- are reduced to the mean of the K LARGEST,
  * K = int(topk * M) for topk < 1, else K = M (the plain mean; 0 for an empty population).  `thickness` > 1 dilates the
  * detached transient weights of cross_entropy_l with a 1 x thickness box filter, zero padded (losses.py:91-95).
- * n_rays <= 4096.  hyper (device): lambda_geo_d, lambda_geo_f, cross-entropy weight, lambda_reg, lambda_ent.      */
+ * n_rays <= 4096 (nsff_nerfw_loss) or <= NSFF_LOSS_MAX_RAYS (nsff_nerfw_loss_ex, below).
+ * hyper (device): lambda_geo_d, lambda_geo_f, cross-entropy weight, lambda_reg, lambda_ent.                       */
 typedef struct NsffLossArgs {
     int64_t n_rays; int32_t n_samples; int32_t n_keep;   /* n_keep = int(n_samples * z_far): samples the regularisers see */
     int32_t n_frames; int32_t max_t;
@@ -491,6 +492,19 @@ typedef struct NsffLossArgs {
     float* g_xyzs_fw_bw; float* g_xyzs_bw_fw; float* g_xyzs_fw; float* g_xyzs_bw;
 } NsffLossArgs;
 int nsff_nerfw_loss(const NsffLossArgs* args, int mode, void* stream);
+/* The same objective for up to NSFF_LOSS_MAX_RAYS rays: the medians and the top-k selection, which nsff_nerfw_loss ranks inside
+ * one workgroup's LDS (hence its 4096 rays), run as an exact radix select over many workgroups -- same definition of the result
+ * (lower median, the K largest, ties to the lower index), any n_rays from 1.  `work`: device memory of at least
+ * nsff_nerfw_loss_work_bytes(n_rays) bytes, 16-byte aligned, owned by the caller, contents irrelevant before and after a call
+ * (mode 2 does not touch it); a null (NSFF_ERR_NULL), misaligned (NSFF_ERR_ALIGN) or too small workspace and n_rays outside
+ * 1 .. NSFF_LOSS_MAX_RAYS (NSFF_ERR_INVALID) are refused before anything is launched.  Asynchronous on `stream`, allocates nothing, capturable.  nsff_nerfw_loss_work_bytes is host
+ * arithmetic: positive and non-decreasing up to the bound, 0 outside it.
+ * nsff_last_loss_path(): which of the two the last loss call of this process launched -- 0 none yet, 1 rank counting
+ * (nsff_nerfw_loss), 2 radix select (nsff_nerfw_loss_ex).                                                          */
+#define NSFF_LOSS_MAX_RAYS 1048576
+size_t nsff_nerfw_loss_work_bytes(long long n_rays);
+int nsff_nerfw_loss_ex(const NsffLossArgs* args, int mode, void* work, size_t work_bytes, void* stream);
+int nsff_last_loss_path(void);
 
 /* ---- a4: coarse sample placement (reference rendering.py:314-324,332) ----
  * zs[n][i] = z_lin[i]                                   (perturb == 0)

@@ -240,6 +240,9 @@ _SIGNATURES = {
     "nsff_composite_backward": (C.c_int, [C.POINTER(CompositeBwdArgs), _fp]),
     "nsff_flow_grad": (C.c_int, [C.POINTER(FlowGradArgs), _fp]),
     "nsff_nerfw_loss": (C.c_int, [C.POINTER(LossArgs), C.c_int, _fp]),
+    "nsff_nerfw_loss_work_bytes": (C.c_size_t, [C.c_longlong]),
+    "nsff_nerfw_loss_ex": (C.c_int, [C.POINTER(LossArgs), C.c_int, _fp, C.c_size_t, _fp]),
+    "nsff_last_loss_path": (C.c_int, []),
     "nsff_splat_planes": (C.c_int, [C.POINTER(SplatArgs), _fp]),
     "nsff_splat_work_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_mpi_composite": (C.c_int, [C.POINTER(MpiArgs), _fp]),
@@ -910,8 +913,10 @@ def flow_grad(zs, z_far, out, accumulate, col_a=-1, g_a=(), col_b=-1, g_b=()):
     _check(load().nsff_flow_grad(C.byref(a), _stream()), "nsff_flow_grad")
 
 
-def nerfw_loss(mode, n_rays, n_samples, n_keep, n_frames, max_t, topk=1.0, thickness=1, **tensors):
-    """mode 1: the terms into tensors['terms']; mode 2: gradients into tensors['g_*'] (include/nsff_render.h)."""
+def nerfw_loss(mode, n_rays, n_samples, n_keep, n_frames, max_t, topk=1.0, thickness=1, work=None, **tensors):
+    """mode 1: the terms into tensors['terms']; mode 2: gradients into tensors['g_*'] (include/nsff_render.h).
+    work: None = nsff_nerfw_loss (rank counting, <= 4096 rays); a uint8 GPU tensor of nerfw_loss_work_bytes(n_rays) bytes =
+    nsff_nerfw_loss_ex (radix select, <= LOSS_MAX_RAYS rays)."""
     a = LossArgs(n_rays=int(n_rays), n_samples=int(n_samples), n_keep=int(n_keep), n_frames=int(n_frames), max_t=int(max_t),
                  topk=float(topk), thickness=int(thickness))
     for k, v in tensors.items():
@@ -924,7 +929,25 @@ def nerfw_loss(mode, n_rays, n_samples, n_keep, n_frames, max_t, topk=1.0, thick
             setattr(a, k, v.data_ptr())
         else:
             setattr(a, k, _ptr(v))
-    _check(load().nsff_nerfw_loss(C.byref(a), int(mode), _stream()), "nsff_nerfw_loss")
+    if work is None:
+        _check(load().nsff_nerfw_loss(C.byref(a), int(mode), _stream()), "nsff_nerfw_loss")
+        return
+    if not (torch.is_tensor(work) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+        raise TypeError("nerfw_loss: work must be a contiguous uint8 GPU tensor")
+    _check(load().nsff_nerfw_loss_ex(C.byref(a), int(mode), work.data_ptr(), work.numel(), _stream()), "nsff_nerfw_loss_ex")
+
+
+LOSS_MAX_RAYS = 1 << 20                       # NSFF_LOSS_MAX_RAYS
+
+
+def nerfw_loss_work_bytes(n_rays):
+    """bytes of workspace nsff_nerfw_loss_ex needs for n_rays rays (0: outside 1 .. LOSS_MAX_RAYS)"""
+    return int(load().nsff_nerfw_loss_work_bytes(int(n_rays)))
+
+
+def last_loss_path():
+    """which selection the last loss call of this process launched: 0 none yet, 1 rank counting, 2 radix select"""
+    return int(load().nsff_last_loss_path())
 
 
 def splat_work_bytes(H, W, S):

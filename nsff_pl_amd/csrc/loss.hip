@@ -13,6 +13,9 @@
 //                       coef[k][n] = weight_n [rank < K] / K, term_k = sum of the selected values / K
 //   loss_stats2_kernel  (backward) the second-level sums the gradient of the depth term needs, with those coefficients
 //   loss_rays_kernel<2> the gradient of sum_k w_k * term_k w.r.t. every consumed render tensor
+// Up to 4096 rays (nsff_nerfw_loss) the two selection steps rank inside one workgroup's LDS as listed; above, and up to
+// NSFF_LOSS_MAX_RAYS = 1 048 576 rays, nsff_nerfw_loss_ex runs them as a radix select over many workgroups in a caller-provided
+// workspace (sel_*_kernel below, same definition of the result); every other kernel is shared.
 // Bound: HBM (reads ~70 B/sample, writes ~50 B/sample in mode 2); a few microseconds per launch at 1024 x 192.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -424,14 +427,237 @@ __global__ __launch_bounds__(256) void loss_rays_kernel(const NsffLossArgs a) {
     }   // rays of this wave
 }
 
-}  // namespace
+// ================= the two selection steps above MAXN rays: an exact radix select over several workgroups =================
+// Same definition of the result as loss_median_kernel / loss_select_kernel.  Every value becomes an order-preserving 32-bit key
+// (sign flip; -0 counts as +0, as `==` does in the rank counting) -- ascending for the medians, complemented for the terms, so
+// that both families ask the same question: which elements are the `target + 1` smallest in (key, index) order?  Four passes of
+// 8 bits, most significant first, find the key T of rank `target`: pass p counts, per vector, the digit p of the elements whose
+// higher digits equal the prefix found so far (LDS histogram per wave, then integer atomicAdd into the global one: integer sums
+// do not depend on their order, so the result is deterministic).  No kernel picks the digit: every wave of the NEXT launch reads
+// the 256 counters of the passes before it and redoes that small prefix scan itself (sel_resolve).  After pass 3, T, the number
+// r of T-valued elements still wanted and their total c are known.  r < c (ties across the cut) needs the index-ordered prefix
+// count of T-valued elements: per-workgroup counts (sel_count_kernel), summed over the workgroups before one's own, plus a ballot
+// prefix inside the workgroup (sel_finish_kernel; workgroup b owns the SEL_CHUNK consecutive indices from b * SEL_CHUNK).
+// sel_finish_kernel writes ST_MED / ST_IDX or coef and a float64 partial sum per workgroup; sel_terms_kernel adds those in index
+// order: terms do not depend on the launch order either.
+constexpr int SEL_NV = N_TERMS;                    // vectors per family (3 medians use the first three slots)
+constexpr int SEL_CHUNK = 1024;                    // consecutive elements per workgroup
+constexpr long long SEL_MAXN = 1 << 20;            // NSFF_LOSS_MAX_RAYS
+constexpr size_t SEL_HIST_WORDS = 4 * SEL_NV * 256;     // per family: [pass][vector][digit]
 
-extern "C" {
+struct SelWork {
+    unsigned* hist;        // [2 families][4][SEL_NV][256], zero at the start of a call
+    unsigned* count;       // [SEL_NV][nb] T-valued elements per workgroup
+    double* partial;       // [SEL_NV][nb] sum of the selected values per workgroup
+    int nb;
+};
+__host__ __device__ inline size_t sel_hist_bytes() { return 2 * SEL_HIST_WORDS * sizeof(unsigned); }
+inline int sel_blocks(long long n) { return (int)((n + SEL_CHUNK - 1) / SEL_CHUNK); }
+inline size_t sel_work_bytes(long long n) {
+    if (n < 1 || n > SEL_MAXN) return 0;
+    const size_t nb = (size_t)sel_blocks(n);
+    const size_t cnt = ((size_t)SEL_NV * nb * sizeof(unsigned) + 15) & ~(size_t)15;
+    return sel_hist_bytes() + cnt + (size_t)SEL_NV * nb * sizeof(double);
+}
 
-int nsff_nerfw_loss(const NsffLossArgs* args, int mode, void* stream) {
-    if (!args) return NSFF_ERR_NULL;
-    const NsffLossArgs& a = *args;
-    if (a.n_rays < 1 || a.n_rays > MAXN || a.n_samples < 2 || a.n_frames < 1 || a.max_t < 0) return NSFF_ERR_INVALID;
+__device__ __forceinline__ unsigned sel_key_asc(float x) {
+    if (x == 0.f) x = 0.f;                                  // -0 == +0
+    const unsigned u = __float_as_uint(x);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+// element i of vector v: its value, whether it belongs to the population, its key
+template <bool MED>
+__device__ __forceinline__ bool sel_load(const NsffLossArgs& a, const float* src, int v, int i, float& x, unsigned& key) {
+    if (MED) { x = v == 2 ? -src[i] : src[i]; key = sel_key_asc(x); return true; }
+    x = src[i];
+    key = ~sel_key_asc(x);
+    return !((v == T_FLOW_FW || v == T_FLOW_BW) && x < 0.f);
+}
+template <bool MED>
+__device__ __forceinline__ const float* sel_src(const NsffLossArgs& a, int v) {
+    if (MED) return v == 0 ? a.depth_fine : (v == 1 ? a.depth_coarse : a.disps);
+    return a.per_ray + (long long)v * a.n_rays;
+}
+
+struct SelState {
+    unsigned prefix;       // the digits found so far (after four passes: T)
+    int rem;               // rank still to descend inside the prefix (after four passes: r - 1)
+    int cnt;               // elements under the prefix (after four passes: c)
+    int M; long long K;    // population, number of elements to select
+    bool rank;             // a threshold is needed at all (medians: always; terms: 0 < K < M)
+};
+// What the passes 0 .. npass-1 found for vector v, from their global histograms.  Called by whole waves; every lane returns
+// the same state.  hist: this family's [4][SEL_NV][256].
+template <bool MED>
+__device__ __forceinline__ SelState sel_resolve(const unsigned* hist, int v, int npass, int N, double topk) {
+    const int lane = threadIdx.x & 63;
+    SelState s; s.prefix = 0u; s.rem = 0; s.cnt = 0; s.M = N; s.K = 0; s.rank = MED;
+    for (int p = 0; p < npass; ++p) {
+        const uint4 q = *reinterpret_cast<const uint4*>(hist + ((size_t)p * SEL_NV + v) * 256 + lane * 4);
+        const int c[4] = {(int)q.x, (int)q.y, (int)q.z, (int)q.w};
+        const int tot = c[0] + c[1] + c[2] + c[3];
+        int incl = tot;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
+        if (p == 0) {
+            s.M = __shfl(incl, 63);
+            s.K = topk >= 1.0 ? (long long)s.M : (long long)(topk * (double)s.M);
+            if (!MED) s.rank = s.K > 0 && s.K < (long long)s.M;
+            if (!s.rank || s.M < 1) { s.rank = false; return s; }
+            s.rem = MED ? (N - 1) / 2 : (int)(s.K - 1);
+            s.cnt = s.M;
+        }
+        int run = incl - tot, d = -1, nr = 0, cn = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (d < 0 && s.rem >= run && s.rem < run + c[j]) { d = lane * 4 + j; nr = s.rem - run; cn = c[j]; }
+            run += c[j];
+        }
+        const unsigned long long hit = __ballot(d >= 0);
+        const int from = hit != 0ull ? (int)__builtin_ctzll(hit) : 0;
+        d = __shfl(d, from); nr = __shfl(nr, from); cn = __shfl(cn, from);
+        s.prefix = (s.prefix << 8) | (unsigned)(d & 255);
+        s.rem = nr; s.cnt = cn;
+    }
+    return s;
+}
+
+// does the index order among the T-valued elements matter?  Terms: only when fewer than all of them are wanted; medians: whenever
+// there is more than one (the element of tie rank r - 1 is THE median)
+template <bool MED>
+__device__ __forceinline__ bool sel_ties(const SelState& s) { return s.rank && (MED ? s.cnt > 1 : s.rem + 1 != s.cnt); }
+
+__device__ __forceinline__ int block_sum_int(int v, int* sRed) {           // 256 threads
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sRed[0] + sRed[1] + sRed[2] + sRed[3];
+}
+
+// zero both families' histograms (a kernel, not hipMemsetAsync: with the memset a replayed capture of the call saw empty histograms)
+__global__ __launch_bounds__(256) void sel_clear_kernel(const SelWork w) {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 2 * SEL_HIST_WORDS / 4) reinterpret_cast<uint4*>(w.hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// pass `p` of the digit histograms; grid (nb, vectors)
+template <bool MED>
+__global__ __launch_bounds__(256) void sel_hist_kernel(const NsffLossArgs a, const SelWork w, const int p) {
+    __shared__ unsigned sH[4][256];
+    const int N = (int)a.n_rays, v = blockIdx.y, wave = threadIdx.x >> 6;
+    const float* src = sel_src<MED>(a, v);
+    if (src == nullptr) return;
+    unsigned* hist = w.hist + (MED ? 0 : SEL_HIST_WORDS);
+    const SelState s = sel_resolve<MED>(hist, v, p, N, a.topk);
+    if (p > 0 && !s.rank) return;
+    for (int j = threadIdx.x; j < 4 * 256; j += 256) (&sH[0][0])[j] = 0u;
+    __syncthreads();
+    const int lo = blockIdx.x * SEL_CHUNK, hi = min(lo + SEL_CHUNK, N);
+    const int shift = 24 - 8 * p;
+    for (int i = lo + threadIdx.x; i < hi; i += 256) {
+        float x; unsigned key;
+        const bool in_pop = sel_load<MED>(a, src, v, i, x, key);
+        if (in_pop && (p == 0 || (key >> (shift + 8)) == s.prefix)) atomicAdd(&sH[wave][(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const unsigned t = sH[0][threadIdx.x] + sH[1][threadIdx.x] + sH[2][threadIdx.x] + sH[3][threadIdx.x];
+    if (t != 0u) atomicAdd(hist + ((size_t)p * SEL_NV + v) * 256 + threadIdx.x, t);
+}
+
+// T-valued elements per workgroup, only where the cut goes through a run of equal values
+template <bool MED>
+__global__ __launch_bounds__(256) void sel_count_kernel(const NsffLossArgs a, const SelWork w) {
+    __shared__ int sRed[4];
+    const int N = (int)a.n_rays, v = blockIdx.y;
+    const float* src = sel_src<MED>(a, v);
+    if (src == nullptr) return;
+    const SelState s = sel_resolve<MED>(w.hist + (MED ? 0 : SEL_HIST_WORDS), v, 4, N, a.topk);
+    if (!sel_ties<MED>(s)) return;
+    const int lo = blockIdx.x * SEL_CHUNK, hi = min(lo + SEL_CHUNK, N);
+    int n = 0;
+    for (int i = lo + threadIdx.x; i < hi; i += 256) {
+        float x; unsigned key;
+        n += (sel_load<MED>(a, src, v, i, x, key) && key == s.prefix) ? 1 : 0;
+    }
+    n = block_sum_int(n, sRed);
+    if (threadIdx.x == 0) w.count[(size_t)v * w.nb + blockIdx.x] = (unsigned)n;
+}
+
+// medians: ST_MED / ST_IDX; terms: coef and the workgroup's sum of the selected values
+template <bool MED>
+__global__ __launch_bounds__(256) void sel_finish_kernel(const NsffLossArgs a, const SelWork w) {
+    __shared__ int sRed[4];
+    __shared__ int sTie[4];
+    __shared__ double sSum[4];
+    const int N = (int)a.n_rays, v = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* src = sel_src<MED>(a, v);
+    if (src == nullptr) return;
+    const SelState s = sel_resolve<MED>(w.hist + (MED ? 0 : SEL_HIST_WORDS), v, 4, N, a.topk);
+    const bool ties = sel_ties<MED>(s);
+    int before = 0;                                           // T-valued elements with a lower index, so far
+    if (ties) {
+        int n = 0;
+        for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) n += (int)w.count[(size_t)v * w.nb + b];
+        before = block_sum_int(n, sRed);
+    }
+    const int lo = blockIdx.x * SEL_CHUNK;
+    const float kf = (float)s.K;
+    double mine = 0.0;
+    for (int r0 = 0; r0 < SEL_CHUNK; r0 += 256) {             // whole workgroup in every round (barriers below)
+        const int i = lo + r0 + threadIdx.x;
+        float x = 0.f; unsigned key = 0u;
+        const bool in_pop = i < N && sel_load<MED>(a, src, v, i, x, key);
+        const bool at = s.rank && in_pop && key == s.prefix;
+        int tie_rank = 0;
+        if (ties) {
+            const unsigned long long m = __ballot(at);
+            tie_rank = __popcll(m & ((1ull << lane) - 1ull));
+            __syncthreads();
+            if (lane == 0) sTie[wave] = __popcll(m);
+            __syncthreads();
+            for (int q = 0; q < wave; ++q) tie_rank += sTie[q];
+            tie_rank += before;
+            before += sTie[0] + sTie[1] + sTie[2] + sTie[3];
+        }
+        if (MED) {
+            if (at && (!ties || tie_rank == s.rem)) {
+                a.stats[ST_MED + v] = x; a.stats[ST_IDX + v] = __int_as_float(i);
+            }
+        } else if (i < N) {
+            bool sel = in_pop && s.K > 0;
+            if (sel && s.rank) sel = key < s.prefix || (at && (!ties || tie_rank <= s.rem));
+            const float wt = a.weights != nullptr ? a.weights[i] : 1.0f;
+            a.coef[(long long)v * N + i] = sel ? wt / kf : 0.f;
+            mine += sel ? (double)x : 0.0;
+        }
+    }
+    if (!MED) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+        __syncthreads();
+        if (lane == 0) sSum[wave] = mine;
+        __syncthreads();
+        if (threadIdx.x == 0) w.partial[(size_t)v * w.nb + blockIdx.x] = (sSum[0] + sSum[1]) + (sSum[2] + sSum[3]);
+    }
+}
+
+// term k = (sum of the workgroups' partial sums, in index order) / K; one wave per term
+__global__ __launch_bounds__(64) void sel_terms_kernel(const NsffLossArgs a, const SelWork w) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const SelState s = sel_resolve<false>(w.hist + SEL_HIST_WORDS, k, 1, (int)a.n_rays, a.topk);
+    double t = 0.0;
+    for (int b = lane; b < w.nb; b += 64) t += w.partial[(size_t)k * w.nb + b];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+    if (lane == 0) a.terms[k] = s.K > 0 ? (float)(t / (double)s.K) : 0.f;
+}
+
+int g_last_loss_path = 0;      // nsff_last_loss_path
+
+int loss_validate(const NsffLossArgs& a, int mode, long long max_rays) {
+    if (a.n_rays < 1 || a.n_rays > max_rays || a.n_samples < 2 || a.n_frames < 1 || a.max_t < 0) return NSFF_ERR_INVALID;
     if (a.n_keep < 1 || a.n_keep > a.n_samples) return NSFF_ERR_INVALID;
     if (mode != 1 && mode != 2) return NSFF_ERR_INVALID;
     if (!a.rgb_fine || !a.depth_fine || !a.rgbs || !a.disps || !a.ts || !a.Ks || !a.Ps || !a.uv_fw || !a.uv_bw ||
@@ -440,10 +666,71 @@ int nsff_nerfw_loss(const NsffLossArgs* args, int mode, void* stream) {
         !a.stats || !a.hyper) return NSFF_ERR_NULL;
     if ((a.rgb_coarse == nullptr) != (a.depth_coarse == nullptr)) return NSFF_ERR_INVALID;
     if (!a.per_ray || !a.coef || a.thickness < 1 || !(a.topk > 0.0)) return NSFF_ERR_INVALID;
+    if (mode == 1) return a.terms ? NSFF_OK : NSFF_ERR_NULL;
+    if (!a.term_w || !a.g_rgb_fine || !a.g_depth_fine || !a.g_t_weights || !a.g_s_weights || !a.g_xyz_fw || !a.g_xyz_bw ||
+        !a.g_rgb_fw || !a.g_rgb_bw || !a.g_xyzs_fw_bw || !a.g_xyzs_bw_fw || !a.g_xyzs_fw || !a.g_xyzs_bw) return NSFF_ERR_NULL;
+    if (a.rgb_coarse && (!a.g_rgb_coarse || !a.g_depth_coarse)) return NSFF_ERR_NULL;
+    return NSFF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nsff_nerfw_loss_work_bytes(long long n_rays) { return sel_work_bytes(n_rays); }
+int nsff_last_loss_path(void) { return g_last_loss_path; }
+
+int nsff_nerfw_loss_ex(const NsffLossArgs* args, int mode, void* work, size_t work_bytes, void* stream) {
+    if (!args) return NSFF_ERR_NULL;
+    const NsffLossArgs& a = *args;
+    if (a.n_rays < 1 || a.n_rays > SEL_MAXN) return NSFF_ERR_INVALID;
+    if (!work) return NSFF_ERR_NULL;
+    if (((uintptr_t)work & 15) != 0) return NSFF_ERR_ALIGN;
+    if (work_bytes < sel_work_bytes(a.n_rays)) return NSFF_ERR_INVALID;
+    const int rc = loss_validate(a, mode, SEL_MAXN);
+    if (rc != NSFF_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((a.n_rays + 3) / 4);
+    if (mode == 2) {                              // the backward needs no selection: the two launches of nsff_nerfw_loss
+        hipLaunchKernelGGL(loss_stats2_kernel, dim3(1), dim3(1024), 0, st, a);
+        hipLaunchKernelGGL(loss_rays_kernel<2>, dim3(blocks), dim3(256), 0, st, a);
+        g_last_loss_path = 2;
+        return nsff_launch_status();
+    }
+    SelWork w;
+    w.nb = sel_blocks(a.n_rays);
+    w.hist = (unsigned*)work;
+    const size_t cnt = ((size_t)SEL_NV * w.nb * sizeof(unsigned) + 15) & ~(size_t)15;
+    w.count = (unsigned*)((char*)work + sel_hist_bytes());
+    w.partial = (double*)((char*)work + sel_hist_bytes() + cnt);
+    const bool ranked = a.topk < 1.0;             // plain means need the populations (pass 0) only
+    const hipError_t e = hipMemsetAsync(a.stats, 0, ST_SIZE * sizeof(float), st);
+    if (e != hipSuccess) return nsff_hip_fail(e);
+    hipLaunchKernelGGL(sel_clear_kernel, dim3((unsigned)((2 * SEL_HIST_WORDS / 4 + 255) / 256)), dim3(256), 0, st, w);
+    const long long total = a.n_rays * a.n_samples;
+    const dim3 gm((unsigned)w.nb, 3), gs((unsigned)w.nb, N_TERMS);
+    hipLaunchKernelGGL(loss_sums_kernel, dim3((unsigned)std::min<long long>((total + 2047) / 2048, 256)), dim3(256), 0, st, a);
+    for (int p = 0; p < 4; ++p) hipLaunchKernelGGL(sel_hist_kernel<true>, gm, dim3(256), 0, st, a, w, p);
+    hipLaunchKernelGGL(sel_count_kernel<true>, gm, dim3(256), 0, st, a, w);
+    hipLaunchKernelGGL(sel_finish_kernel<true>, gm, dim3(256), 0, st, a, w);
+    hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(loss_rays_kernel<1>, dim3(blocks), dim3(256), 0, st, a);
+    for (int p = 0; p < (ranked ? 4 : 1); ++p) hipLaunchKernelGGL(sel_hist_kernel<false>, gs, dim3(256), 0, st, a, w, p);
+    if (ranked) hipLaunchKernelGGL(sel_count_kernel<false>, gs, dim3(256), 0, st, a, w);
+    hipLaunchKernelGGL(sel_finish_kernel<false>, gs, dim3(256), 0, st, a, w);
+    hipLaunchKernelGGL(sel_terms_kernel, dim3(N_TERMS), dim3(64), 0, st, a, w);
+    g_last_loss_path = 2;
+    return nsff_launch_status();
+}
+
+int nsff_nerfw_loss(const NsffLossArgs* args, int mode, void* stream) {
+    if (!args) return NSFF_ERR_NULL;
+    const NsffLossArgs& a = *args;
+    const int rc = loss_validate(a, mode, MAXN);
+    if (rc != NSFF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((a.n_rays + 3) / 4);
     if (mode == 1) {
-        if (!a.terms) return NSFF_ERR_NULL;
         hipError_t e = hipMemsetAsync(a.stats, 0, ST_SIZE * sizeof(float), st);
         if (e == hipSuccess) e = hipMemsetAsync(a.terms, 0, N_TERMS * sizeof(float), st);
         if (e != hipSuccess) return nsff_hip_fail(e);
@@ -454,12 +741,10 @@ int nsff_nerfw_loss(const NsffLossArgs* args, int mode, void* stream) {
         hipLaunchKernelGGL(loss_rays_kernel<1>, dim3(blocks), dim3(256), 0, st, a);
         hipLaunchKernelGGL(loss_select_kernel, dim3((unsigned)((a.n_rays + 255) / 256), N_TERMS), dim3(256), 0, st, a);
     } else {
-        if (!a.term_w || !a.g_rgb_fine || !a.g_depth_fine || !a.g_t_weights || !a.g_s_weights || !a.g_xyz_fw || !a.g_xyz_bw ||
-            !a.g_rgb_fw || !a.g_rgb_bw || !a.g_xyzs_fw_bw || !a.g_xyzs_bw_fw || !a.g_xyzs_fw || !a.g_xyzs_bw) return NSFF_ERR_NULL;
-        if (a.rgb_coarse && (!a.g_rgb_coarse || !a.g_depth_coarse)) return NSFF_ERR_NULL;
         hipLaunchKernelGGL(loss_stats2_kernel, dim3(1), dim3(1024), 0, st, a);
         hipLaunchKernelGGL(loss_rays_kernel<2>, dim3(blocks), dim3(256), 0, st, a);
     }
+    g_last_loss_path = 1;
     return nsff_launch_status();
 }
 

@@ -1,12 +1,17 @@
-"""``NeRFWLoss`` as six small HIP launches forward + two backward (csrc/loss.hip, ``nsff_nerfw_loss``).
+"""``NeRFWLoss`` as a handful of HIP launches forward + two backward (csrc/loss.hip).
 
 The torch expression in :mod:`nsff_pl_amd.losses` is ~280 small kernels forward and ~300 backward -- a quarter of the
-C4 training step's device time.  For the NSFF train-mode configuration (flows + disocclusion in the dict, <= 4096 rays on
-the GPU) the same eleven scalars and their gradients w.r.t. the render dict come from the kernels instead, for every
-reduction the reference's constructor can ask for: plain means, per-ray ``weights``, ``topk < 1`` (mean of the
-int(topk * M) largest per-ray values, losses.py:162-169) and ``thickness > 1`` (dilated cross entropy, losses.py:91-95).
-The torch expression stays what static-only models and CPU tensors use, and what the kernels are tested against
-(tests/test_losses.py).  ``NSFF_FUSED_LOSS=0`` switches the kernels off.
+C4 training step's device time.  For the NSFF train-mode configuration (flows + disocclusion in the dict, fp32 on the GPU,
+at most ``MAX_RAYS_SELECT`` = 1 048 576 rays) the same eleven scalars and their gradients w.r.t. the render dict come from the
+kernels instead, for every reduction the reference's constructor can ask for: plain means, per-ray ``weights``, ``topk < 1``
+(mean of the int(topk * M) largest per-ray values, losses.py:162-169) and ``thickness > 1`` (dilated cross entropy,
+losses.py:91-95).  Up to ``MAX_RAYS`` = 4096 rays the medians and the top-k selection rank inside one workgroup's LDS
+(``nsff_nerfw_loss``: six launches forward); above, the same two steps run as an exact radix select over many workgroups in a
+workspace allocated once per (device, batch size) (``nsff_nerfw_loss_ex``: 12 launches forward, 17 with ``topk < 1``).
+``_lib.last_loss_path()`` reports which of the two ran.  The torch expression stays what static-only models and CPU tensors
+use, and what the kernels are tested against (tests/test_losses.py, tests/test_loss_large_gpu.py).
+``NSFF_FUSED_LOSS=0`` switches the kernels off; ``NSFF_LOSS_SELECT=radix`` takes the radix select at every size,
+``NSFF_LOSS_SELECT=rank`` never (more than 4096 rays are then the torch expression's).
 """
 import os
 
@@ -26,12 +31,34 @@ _INPUTS = (("rgb_fine", "rgb_fine", "g_rgb_fine"), ("rgb_coarse", "rgb_coarse", 
            ("disocc_fw", "disocc_fw", None), ("disocc_bw", "disocc_bw", None), ("disoccs_fw", "disoccs_fw", None),
            ("disoccs_bw", "disoccs_bw", None), ("xyzs_fine", "xyzs_fine", None))
 _OPTIONAL = ("rgb_coarse", "depth_coarse")
-MAX_RAYS = 4096
+MAX_RAYS = 4096                         # the rank-counting path (nsff_nerfw_loss)
+MAX_RAYS_SELECT = _lib.LOSS_MAX_RAYS    # the radix-select path (nsff_nerfw_loss_ex), NSFF_LOSS_MAX_RAYS
 _CONST = {}
+_WORK = {}
 
 
 def enabled():
     return os.environ.get("NSFF_FUSED_LOSS", "1") != "0"
+
+
+def select_path(n_rays):
+    """'rank', 'radix' or None (no kernel path) for a batch of n_rays rays"""
+    mode = os.environ.get("NSFF_LOSS_SELECT", "")
+    if mode not in ("", "rank", "radix"):
+        raise ValueError(f"NSFF_LOSS_SELECT={mode!r}: expected 'rank' or 'radix'")
+    if mode != "radix" and 1 <= n_rays <= MAX_RAYS:
+        return "rank"
+    if mode != "rank" and 1 <= n_rays <= MAX_RAYS_SELECT:
+        return "radix"
+    return None
+
+
+def _workspace(dev, n_rays):
+    """the radix select's scratch, allocated once per (device, batch size): before any graph capture, the eager warm-up has"""
+    key = (dev, n_rays)
+    if key not in _WORK:
+        _WORK[key] = torch.empty(_lib.nerfw_loss_work_bytes(n_rays), dtype=torch.uint8, device=dev)
+    return _WORK[key]
 
 
 def applicable(loss, inputs, targets, kwargs):
@@ -41,7 +68,7 @@ def applicable(loss, inputs, targets, kwargs):
     w = kwargs.get("weights")
     if w is not None and not (torch.is_tensor(w) and x is not None and w.numel() == x.shape[0]):
         return False
-    if x is None or not x.is_cuda or x.dtype != torch.float32 or not 1 <= x.shape[0] <= MAX_RAYS:
+    if x is None or not x.is_cuda or x.dtype != torch.float32 or select_path(x.shape[0]) is None:
         return False
     need = [k for k, _, _ in _INPUTS if k not in _OPTIONAL]
     if any(k not in inputs for k in need) or ("rgb_coarse" in inputs) != ("depth_coarse" in inputs):
@@ -59,7 +86,8 @@ class _LossFn(torch.autograd.Function):
         terms = torch.empty(len(TERMS), device=dev)
         common = dict(cfg["targets"], hyper=hyper, stats=stats, weights=cfg["weights"],
                       per_ray=torch.empty(len(TERMS), cfg["n"], device=dev), coef=torch.empty(len(TERMS), cfg["n"], device=dev),
-                      topk=cfg["topk"], thickness=cfg["thickness"])
+                      topk=cfg["topk"], thickness=cfg["thickness"],
+                      work=_workspace(dev, cfg["n"]) if select_path(cfg["n"]) == "radix" else None)
         _lib.nerfw_loss(1, cfg["n"], cfg["s"], cfg["n_keep"], cfg["n_frames"], cfg["max_t"], terms=terms, **args, **common)
         ctx.cfg, ctx.args, ctx.common = cfg, args, common
         return terms

@@ -2,7 +2,8 @@
 
 A restatement of the reference's ``losses.py`` (``shiftscale_invariant_depthloss`` :8-28, ``NeRFWLoss``
 :31-171) with the same constructor, term names, weights and reductions.  On the GPU the NSFF train configuration
-is evaluated -- forward and backward -- by the fused kernels of ``csrc/loss.hip`` (:mod:`nsff_pl_amd.fused_loss`);
+is evaluated -- forward and backward -- by the fused kernels of ``csrc/loss.hip`` (:mod:`nsff_pl_amd.fused_loss`, up to
+1 048 576 rays);
 the torch expression below is the general form (top-k mining, per-ray weights, dilated cross entropy, static-only
 models, CPU tensors) and what the kernels are tested against.  ``kornia.filter2d`` (1 x thickness box filter, zero padded) is replaced by ``conv1d``.
 ``Ks`` (n_cam,3,3), ``Ps`` (n_cam,N_frames,3,4) and ``max_t`` are attached by the trainer exactly like

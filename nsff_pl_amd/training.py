@@ -189,6 +189,8 @@ class NSFFTrainer:
             self.ray_bank.record(batch, results["rgb_fine"])
         if self.graph:
             kwargs["epoch_ramp"] = self._ramp
+        if "weights" in batch:                                           # per-ray loss weights (losses.py:163-164)
+            kwargs["weights"] = batch["weights"]
         loss_d = self.loss(results, batch, epoch=self.current_epoch, **kwargs)
         loss = loss_d.total() if hasattr(loss_d, "total") else sum(loss_d.values())
         with torch.no_grad():
