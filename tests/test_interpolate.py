@@ -3,7 +3,8 @@ rendering.py:365-460 (golden G11) and hand-derived splat cases.
 
 The reference's splat kernel (models/softsplat.py, cupy/CUDA) cannot run in the build container; the golden was
 produced by the reference's `interpolate` with the oracle's splat standing in for it, so G11 pins the projection,
-plane optical flow and MPI compositing; the splat itself is pinned by the known-answer cases below.
+plane optical flow and MPI compositing; the splat itself is pinned by the known-answer cases below (the oracle's) and, for the HIP
+kernels, by tests/test_interp_kernels.py: accumulators of every route against the float64 restatement tests/splat_ref.py.
 """
 import numpy as np
 import pytest
