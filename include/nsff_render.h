@@ -447,6 +447,29 @@ int nsff_adam_step_segments(float* param, const float* grad, float* exp_avg, flo
                             const float* lr, double beta1, double beta2, double eps, double weight_decay,
                             const int64_t* seg_start, int n_seg, int32_t* seg_used, void* stream);
 
+/* The reference's other optimizers (utils/__init__.py:42-50 get_optimizer, --optimizer sgd / radam), on the same flat buffers
+ * with the same conventions: n % 4 == 0, 16-byte aligned, lr a DEVICE scalar, capturable; seg_start / seg_used both NULL (every
+ * element is updated) or both given (the segment form of nsff_adam_step_segments: a tensor whose gradient slice is identically
+ * zero this step keeps its value and its state, torch's `if p.grad is None: continue`).
+ *
+ * torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov:  g' = g + weight_decay * p;
+ * buf = momentum * buf + g';  p -= lr * buf.  momentum_buf starts at zero (that IS torch's first-step buf = g').  With
+ * momentum == 0 the step is p -= lr * g' and momentum_buf is neither read nor written (NULL is fine).
+ * state: DEVICE float[4]; state[0] = number of steps taken so far (the call increments it; the arithmetic does not use it).
+ * One launch (segment form: one memset + two launches).                                                                  */
+int nsff_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float* state, const float* lr,
+                  double momentum, double weight_decay, const int64_t* seg_start, int n_seg, int32_t* seg_used, void* stream);
+
+/* RAdam as torch.optim.RAdam(lr, betas, eps, weight_decay, decoupled_weight_decay=True) evaluates it:  p *= 1 - lr * weight_decay;
+ * m, v as Adam;  rho_inf = 2 / (1 - beta2) - 1,  rho_t = rho_inf - 2 t beta2^t / (1 - beta2^t);
+ * rho_t > 5:  p -= lr / (1 - beta1^t) * r_t * m * sqrt(1 - beta2^t) / (sqrt(v) + eps),
+ *             r_t = sqrt((rho_t - 4)(rho_t - 2) rho_inf / ((rho_inf - 4)(rho_inf - 2) rho_t));   otherwise  p -= lr / (1 - beta1^t) * m.
+ * state: DEVICE float[8]; state[0] = number of steps taken so far (zero it once; the call increments it), state[1..4] scratch
+ * (the per-step scalars, evaluated in double on the device from state[0]).  Two launches (segment form: + memset + one).  */
+int nsff_radam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* state,
+                    const float* lr, double beta1, double beta2, double eps, double weight_decay,
+                    const int64_t* seg_start, int n_seg, int32_t* seg_used, void* stream);
+
 /* ---- N1: the training objective NeRFWLoss (reference losses.py:8-28, 31-171) on the render dict, NSFF train-mode
  * configuration (flows + disocclusion present, topk == 1, no per-ray weights, thickness == 1), every term reduced to
  * its scalar.  mode 1: terms[11] = col_l, disp_l, entropy_l, cross_entropy_l, flow_fw_l, flow_bw_l, pho_l, cyc_l,

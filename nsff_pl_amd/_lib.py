@@ -237,6 +237,9 @@ _SIGNATURES = {
     "nsff_adam_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
     "nsff_adam_step_segments": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, C.c_double, C.c_double, C.c_double, C.c_double,
                                           _fp, C.c_int, _fp, _fp]),
+    "nsff_sgd_step": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp, _fp, C.c_double, C.c_double, _fp, C.c_int, _fp, _fp]),
+    "nsff_radam_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                  _fp, C.c_int, _fp, _fp]),
     "nsff_composite_backward": (C.c_int, [C.POINTER(CompositeBwdArgs), _fp]),
     "nsff_flow_grad": (C.c_int, [C.POINTER(FlowGradArgs), _fp]),
     "nsff_nerfw_loss": (C.c_int, [C.POINTER(LossArgs), C.c_int, _fp]),
@@ -889,6 +892,27 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, state, lr, beta1, beta2, eps, we
                                           C.c_void_p(seg_start.data_ptr()), int(seg_used.numel()),
                                           C.c_void_p(seg_used.data_ptr()), _stream()),
            "nsff_adam_step_segments")
+
+
+def _segments(seg_start, seg_used):
+    if seg_start is None:
+        return None, 0, None
+    return C.c_void_p(seg_start.data_ptr()), int(seg_used.numel()), C.c_void_p(seg_used.data_ptr())
+
+
+def sgd_step(param, grad, momentum_buf, state, lr, momentum, weight_decay, seg_start=None, seg_used=None):
+    """One torch.optim.SGD step (dampening 0, no Nesterov) on flat buffers (include/nsff_render.h: nsff_sgd_step); state / lr are
+    device tensors, ``momentum_buf`` is None when ``momentum == 0``.  ``seg_start`` / ``seg_used`` as in :func:`adam_step`."""
+    _check(load().nsff_sgd_step(_ptr(param), _ptr(grad), _ptr(momentum_buf), param.numel(), _ptr(state), _ptr(lr), float(momentum),
+                                float(weight_decay), *_segments(seg_start, seg_used), _stream()), "nsff_sgd_step")
+
+
+def radam_step(param, grad, exp_avg, exp_avg_sq, state, lr, beta1, beta2, eps, weight_decay, seg_start=None, seg_used=None):
+    """One RAdam step with decoupled weight decay on flat buffers (include/nsff_render.h: nsff_radam_step); state (8 floats) / lr
+    are device tensors.  ``seg_start`` / ``seg_used`` as in :func:`adam_step`."""
+    _check(load().nsff_radam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), _ptr(state), _ptr(lr),
+                                  float(beta1), float(beta2), float(eps), float(weight_decay), *_segments(seg_start, seg_used),
+                                  _stream()), "nsff_radam_step")
 
 
 def composite_backward(n_rays, n_samples, has_transient, flow_mode, noise_std, **tensors):

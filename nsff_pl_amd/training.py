@@ -1,8 +1,8 @@
 """Thin NSFF trainer step around the HIP renderer.
 
 Mirrors what ``NSFFSystem`` of the reference's ``train.py`` does per batch -- ``forward`` (:99-123, the ray
-chunk loop), ``on_train_epoch_start`` (:174-176), ``training_step`` (:178-198) and the Adam / MultiStepLR
-defaults of ``utils/__init__.py:24-77`` + ``opt.py`` -- without pytorch-lightning: one process per GPU, the
+chunk loop), ``on_train_epoch_start`` (:174-176), ``training_step`` (:178-198) and the optimizer / learning-rate schedule options of
+``utils/__init__.py:24-77`` + ``opt.py`` (Adam + MultiStepLR by default) -- without pytorch-lightning: one process per GPU, the
 renderer's forward on the gfx950 kernels, backward through :mod:`nsff_pl_amd.autograd`, and (world > 1)
 ONE flat RCCL all-reduce of the gradients per step instead of DDP's per-bucket hooks (the models total
 2.3 M parameters = 9.2 MB: a single bucket is already far below the xGMI latency/bandwidth knee, so
@@ -16,6 +16,8 @@ Logging, checkpoint callbacks and validation images of the reference are control
 """
 from collections import defaultdict
 
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -24,13 +26,59 @@ from . import metrics
 from . import range_check
 from .autograd import grad_parameters
 from .losses import NeRFWLoss
-from .optim import FlatAdam
+from .optim import FlatAdam, FlatRAdam, FlatSGD
 from .rendering import render_rays
 
 
 def psnr(image_gt, image_pred):
     """metrics.py:6-16 (no mask)."""
     return -10 * torch.log10(torch.mean((image_gt - image_pred) ** 2))
+
+
+OPTIMIZERS = {"sgd": FlatSGD, "adam": FlatAdam, "radam": FlatRAdam}
+LR_SCHEDULERS = ("const", "steplr", "cosine", "poly")
+COSINE_ETA_MIN = 1e-8                       # utils/__init__.py:60,65
+
+
+def lr_at(hp, epoch):
+    """The learning rate during epoch ``epoch`` (0-based): the reference's ``get_scheduler`` (utils/__init__.py:59-76), stepped
+    once per epoch as Lightning steps it, as a pure function of the hparams.
+
+    ========  ==========================================================================
+    const     ``lr``
+    steplr    ``lr * decay_gamma ** #{milestones in decay_step <= e}``  (MultiStepLR)
+    cosine    ``eta_min + (lr - eta_min) (1 + cos(pi e / num_epochs)) / 2``, ``eta_min = 1e-8``  (CosineAnnealingLR)
+    poly      ``lr * (1 - e / num_epochs) ** poly_exp``
+    ========  ==========================================================================
+
+    ``poly``: the reference's own branch raises NameError (``LambdaLR`` is never imported in utils/__init__.py); this is what
+    it evidently means, pinned against ``torch.optim.lr_scheduler.LambdaLR``.
+
+    Warm-up (``warmup_epochs = W > 0``, optimizer sgd or adam; ignored for radam, utils/__init__.py:72) follows the
+    reference's ``GradualWarmupScheduler``: ``lr ((m - 1) e / W + 1)`` for ``e <= W`` with ``m = warmup_multiplier``, then
+    ``m * after(e - W - 1)`` -- the schedule above restarted at its own epoch 0 one epoch late, on the base rate ``m lr``.
+    Deviation: for cosine the reference does NOT follow that rule under current torch.  ``CosineAnnealingLR``'s recursive
+    ``get_lr`` is handed a base rate that was changed under it, and the rate overshoots its peak at ``e = W + 1`` and follows
+    no closed form afterwards (the recorded sequence is in tests/golden/g23_lr_schedules.npz).  That artefact is not
+    reproduced; cosine uses the same clean rule as the other two.  ``warmup_epochs`` defaults to 0."""
+    base, kind = float(hp["lr"]), hp["lr_scheduler"]
+
+    def after(e, lr):
+        if kind == "const":
+            return lr
+        if kind == "steplr":
+            return lr * float(hp["decay_gamma"]) ** sum(1 for m in hp["decay_step"] if m <= e)
+        if kind == "cosine":
+            return COSINE_ETA_MIN + (lr - COSINE_ETA_MIN) * (1 + math.cos(math.pi * e / hp["num_epochs"])) / 2
+        return lr * max(1 - e / hp["num_epochs"], 0.0) ** float(hp["poly_exp"])     # (0 from num_epochs on, not a complex power)
+
+    W = int(hp["warmup_epochs"])
+    if W <= 0 or hp["optimizer"] not in ("sgd", "adam"):
+        return after(epoch, base)
+    m = float(hp["warmup_multiplier"])
+    if epoch <= W:
+        return base * ((m - 1.0) * epoch / W + 1.0)
+    return after(epoch - W - 1, m * base)
 
 
 def allreduce_gradients(params, group=None):
@@ -56,7 +104,9 @@ class NSFFTrainer:
     """models = {'fine', 'coarse'?}, embeddings = {'xyz','dir','t'?,'a'?} exactly as train.py:40-84 builds them.
 
     hparams (attribute or dict access): N_samples, N_importance, perturb, noise_std, chunk, lambda_geo_init,
-    thickness, topk, lr, weight_decay, decay_step, decay_gamma -- reference names and defaults (opt.py) -- and
+    thickness, topk, lr, weight_decay, decay_step, decay_gamma, optimizer ('sgd' | 'adam' | 'radam'), momentum,
+    lr_scheduler ('const' | 'steplr' | 'cosine' | 'poly'), num_epochs, poly_exp, warmup_multiplier, warmup_epochs -- reference
+    names and defaults (opt.py; schedules: :func:`lr_at`) -- and
     decay_unused (False: with weight_decay > 0 a parameter that receives no gradient is left alone, as torch.optim.Adam
     leaves ``grad is None`` parameters alone; True: the plain every-element step, see optim.FlatAdam), and img_wh ((W, H) of
     the validation frames, opt.py's name; None: validation reports val_psnr only).
@@ -68,7 +118,9 @@ class NSFFTrainer:
 
     DEFAULTS = dict(N_samples=128, N_importance=0, perturb=1.0, noise_std=1.0, chunk=32 * 1024,
                     lambda_geo_init=0.04, thickness=1, topk=1.0, lr=5e-4, weight_decay=0.0,
-                    decay_step=[20], decay_gamma=0.1, decay_unused=False, img_wh=None)
+                    decay_step=[20], decay_gamma=0.1, decay_unused=False, img_wh=None,
+                    optimizer="adam", momentum=0.9, lr_scheduler="steplr", num_epochs=16, poly_exp=0.9,
+                    warmup_multiplier=1.0, warmup_epochs=0)
 
     def __init__(self, models, embeddings, n_frames, hparams=None, Ks=None, Ps=None,
                  output_transient=True, output_transient_flow=("fw", "bw", "disocc"), graph=False, optimizer_cls=FlatAdam,
@@ -86,6 +138,15 @@ class NSFFTrainer:
             given = hparams if isinstance(hparams, dict) else vars(hparams)
             hp.update({k: v for k, v in given.items() if k in hp})
         self.hp = hp
+        if hp["optimizer"] == "ranger":
+            raise ValueError("optimizer 'ranger' is not offered: its definition lives only in the torch_optimizer package, which "
+                             "is not available to pin an implementation against, and it is not approximated")
+        if hp["optimizer"] not in OPTIMIZERS:
+            raise ValueError(f"optimizer not recognized: {hp['optimizer']!r} (one of {sorted(OPTIMIZERS)})")
+        if hp["lr_scheduler"] not in LR_SCHEDULERS:
+            raise ValueError(f"scheduler not recognized: {hp['lr_scheduler']!r} (one of {list(LR_SCHEDULERS)})")
+        if hp["warmup_epochs"] > 0 and hp["warmup_multiplier"] < 1.0:        # (utils/warmup_scheduler.py:16-17)
+            raise ValueError("warmup_multiplier should be greater than or equal to 1")
         self.models, self.embeddings, self.n_frames = models, embeddings, n_frames
         self.ray_bank = ray_bank
         self.output_transient = output_transient
@@ -94,7 +155,8 @@ class NSFFTrainer:
         if isinstance(graph, str) and not self._graph_auto:
             raise ValueError("graph must be True, False or 'auto'")
         self.graph = False if self._graph_auto else bool(graph)
-        self.optimizer_cls = optimizer_cls       # (tests drive the step on CPU with a torch-op twin of FlatAdam)
+        # hparams' `optimizer` picks the class; a caller's own class wins (tests drive the step on CPU with torch-op twins)
+        self.optimizer_cls = OPTIMIZERS[hp["optimizer"]] if optimizer_cls is FlatAdam else optimizer_cls
         self.loss = NeRFWLoss(lambda_geo=hp["lambda_geo_init"], thickness=hp["thickness"], topk=hp["topk"],
                               static_shapes=self.graph)
         if self.output_transient_flow:                                   # train.py:136-138
@@ -133,8 +195,9 @@ class NSFFTrainer:
 
     def _make_optimizer(self):
         hp = self.hp
-        self.optimizer = self.optimizer_cls(self.params, lr=hp["lr"], eps=1e-8, weight_decay=hp["weight_decay"],
-                                            decay_unused=hp["decay_unused"])
+        own = dict(momentum=hp["momentum"]) if hp["optimizer"] == "sgd" else dict(eps=1e-8)       # utils/__init__.py:42-50
+        self.optimizer = self.optimizer_cls(self.params, lr=hp["lr"], weight_decay=hp["weight_decay"],
+                                            decay_unused=hp["decay_unused"], **own)
         self._flat_grad = self.optimizer.flat_grad
         self._lr_epoch = -1
 
@@ -407,6 +470,15 @@ class NSFFTrainer:
         return missing
 
     def on_train_epoch_end(self):
-        """MultiStepLR(milestones=decay_step, gamma=decay_gamma) of train.py:143-146, stepped once per epoch."""
-        if self.optimizer is not None and (self.current_epoch + 1) in list(self.hp["decay_step"]):
-            self.optimizer.lr.mul_(self.hp["decay_gamma"])
+        """The learning-rate schedule (:func:`lr_at`), stepped once per epoch as Lightning steps an epoch-interval scheduler:
+        the rate of the NEXT epoch goes into the optimizer's device scalar, which eager steps and captured graphs both read.
+        The default -- MultiStepLR(milestones=decay_step, gamma=decay_gamma) of train.py:143-146 without warm-up -- multiplies
+        the rate in place at each milestone.  After :meth:`load_checkpoint` the schedule continues from the restored epoch."""
+        if self.optimizer is None:
+            return
+        hp = self.hp
+        if hp["lr_scheduler"] == "steplr" and (hp["warmup_epochs"] <= 0 or hp["optimizer"] not in ("sgd", "adam")):
+            if (self.current_epoch + 1) in list(hp["decay_step"]):
+                self.optimizer.lr.mul_(hp["decay_gamma"])
+        elif hp["lr_scheduler"] != "const" or hp["warmup_epochs"] > 0:
+            self.optimizer.set_lr(lr_at(hp, self.current_epoch + 1))
