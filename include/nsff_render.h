@@ -566,6 +566,32 @@ int nsff_warp_points(const float* raw, const float* xyz, const float* zs, int64_
 int nsff_frame_rays(const float* K4_host, const float* c2w_host, int32_t H, int32_t W, float near, float shift_near,
                     int64_t first_pixel, int64_t n_pixels, float* rays, void* stream);
 
+/* ---- the training split's ray bank, built on the device (reference datasets/monocular.py:136-184): the records of frames
+ * [first_frame, first_frame + frame_count) in ONE launch, written to records[frame] in the NSFF_RAY_RECORD column layout:
+ * NDC ray 0-5 (the arithmetic of nsff_frame_rays, bit for bit), rgb 6-8, (float) frame 9, disparity 10, mask 11,
+ * uv + flow_fw 12-13, uv + flow_bw 14-15 with uv = (pix % W, pix / W).  Every input holds all n_frames frames, already at the
+ * target resolution: images (F,H,W,3) and masks (F,H,W) as uint8 (converted by a true division by 255, torchvision's ToTensor)
+ * or fp32, disps (F,H,W) fp32, flow_fw / flow_bw (F,H,W,2) fp32 or NULL (= zero flow).  Frame n_frames-1 gets zero forward flow
+ * and frame 0 zero backward flow whatever the flow tensors hold there (monocular.py:167-179).
+ * frame_table: device (n_frames, NSFF_FRAME_TABLE) fp32 = row-major c2w (3,4) | shift_near = -min(-1, c2w[2][3]) | 3 unused.
+ * n_pixels (the records' second dimension) must equal H * W and be below 2^31; frame_count <= 65535.  records 16-byte, flows 8-byte aligned (NSFF_ERR_ALIGN). */
+#define NSFF_FRAME_TABLE     16
+typedef struct NsffRayRecordArgs {
+    int32_t n_frames, H, W;
+    int32_t first_frame, frame_count;
+    int32_t image_u8, mask_u8;  /* 1: uint8 input, 0: fp32                                  */
+    float   fx, fy, cx, cy, near;
+    int64_t n_pixels;
+    const void*  images;
+    const float* disps;
+    const void*  masks;
+    const float* flow_fw;
+    const float* flow_bw;
+    const float* frame_table;
+    float*       records;       /* (n_frames, n_pixels, NSFF_RAY_RECORD)                    */
+} NsffRayRecordArgs;
+int nsff_ray_records(const NsffRayRecordArgs* args, void* stream);
+
 /* ---- a6: eval-only frustum visibility (reference rendering.py:190-200 with datasets/ray_utils.py:127-151,154-181) ---- */
 typedef struct NsffFrustumArgs {
     const float*   w2c;         /* device (n_cams * n_frames, 12): row-major first three rows of inverse([c2w; 0 0 0 1]),

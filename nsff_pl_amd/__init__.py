@@ -12,6 +12,9 @@ from .range_check import RangeFlags, range_flags
 from .nerf import NeRF, PosEmbedding
 from .rendering import render_rays, sample_pdf
 from .interpolation import interpolate
+from .frames import build_records, projection_matrices
+from .sampling import RayBank
 
 __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "set_precision", "get_precision",
-           "set_range_check", "get_range_check", "range_flags", "RangeFlags"]
+           "set_range_check", "get_range_check", "range_flags", "RangeFlags",
+           "build_records", "projection_matrices", "RayBank"]

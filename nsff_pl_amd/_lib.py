@@ -177,6 +177,17 @@ class RayDrawArgs(C.Structure):
                  ("records", _fp), ("cdf", _fp), ("u", _fp)] + [(n, _fp) for n in _DRAW_OUT])
 
 
+FRAME_TABLE = 16                # floats per frame of nsff_ray_records' table: c2w (3,4) row-major | shift_near | 3 unused
+
+
+class RayRecordArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("first_frame", C.c_int32),
+                ("frame_count", C.c_int32), ("image_u8", C.c_int32), ("mask_u8", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("near", C.c_float),
+                ("n_pixels", C.c_int64), ("images", _fp), ("disps", _fp), ("masks", _fp), ("flow_fw", _fp), ("flow_bw", _fp),
+                ("frame_table", _fp), ("records", _fp)]
+
+
 # name -> (restype, argtypes); also the list of symbols the header declares
 _SIGNATURES = {
     "nsff_abi_version": (C.c_int, []),
@@ -211,6 +222,7 @@ _SIGNATURES = {
     "nsff_frustum_visibility": (C.c_int, [C.POINTER(FrustumArgs), _fp, C.c_int64, _fp, _fp]),
     "nsff_frame_rays": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float,
                                   C.c_float, C.c_int64, C.c_int64, _fp, _fp]),
+    "nsff_ray_records": (C.c_int, [C.POINTER(RayRecordArgs), _fp]),
     "nsff_bwd_packed_bytes": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_size_t)]),
     "nsff_pack_weights_bwd": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(_fp), _fp, _fp]),
     "nsff_field_backward": (C.c_int, [C.POINTER(ModelDesc), _fp, C.POINTER(FieldBwdArgs), _fp]),
@@ -1064,6 +1076,29 @@ def ray_draw(records, frame, u, cdf, out):
         setattr(a, n, _dptr(t, torch.int64 if n in ("ts", "cam_ids", "rand_idx") else torch.float32, f"ray_draw: {n}"))
     with torch.cuda.device(records.device):
         _check(load().nsff_ray_draw(C.byref(a), _stream()), "nsff_ray_draw")
+
+
+def ray_records(K4, frame_table, images, disps, masks, flow_fw, flow_bw, near, first_frame, frame_count, records):
+    """nsff_ray_records: images (F,H,W,3) uint8 / fp32, disps (F,H,W) fp32, masks (F,H,W) uint8 / fp32, flows (F,H,W,2) fp32 or
+    None, frame_table (F, FRAME_TABLE) fp32, all on the GPU -> records[first_frame : first_frame + frame_count] of the
+    (F, H*W, 16) output, one launch."""
+    F, H, W = (int(v) for v in images.shape[:3])
+
+    def either(t, what):
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError(f"{what}: need a uint8 or float32 tensor, got {t.dtype}")
+        return _dptr(t, t.dtype, what)
+    a = RayRecordArgs(n_frames=F, H=H, W=W, first_frame=int(first_frame), frame_count=int(frame_count),
+                      image_u8=int(images.dtype == torch.uint8), mask_u8=int(masks.dtype == torch.uint8),
+                      fx=float(K4[0]), fy=float(K4[1]), cx=float(K4[2]), cy=float(K4[3]), near=float(near),
+                      n_pixels=int(records.shape[1]), images=either(images, "ray_records: images"),
+                      disps=_dptr(disps, torch.float32, "ray_records: disps"), masks=either(masks, "ray_records: masks"),
+                      flow_fw=_dptr(flow_fw, torch.float32, "ray_records: flows_fw"),
+                      flow_bw=_dptr(flow_bw, torch.float32, "ray_records: flows_bw"),
+                      frame_table=_dptr(frame_table, torch.float32, "ray_records: frame table"),
+                      records=_dptr(records, torch.float32, "ray_records: out"))
+    with torch.cuda.device(records.device):
+        _check(load().nsff_ray_records(C.byref(a), _stream()), "nsff_ray_records")
 
 
 def range_flags(out, clear):

@@ -202,33 +202,99 @@ struct FrameRayArgs {
     float* rays;             // (count, 6)
 };
 
-__global__ void frame_rays_kernel(const FrameRayArgs a) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= a.count) return;
-    const long long pix = a.first + idx;
-    const float i = (float)(pix % a.W), j = (float)(pix / a.W);      // no +0.5 pixel centring (ray_utils.py:26)
-    const float dc[3] = {(i - a.cx) / a.fx, -(j - a.cy) / a.fy, -1.0f};
+// One pixel's NDC ray, shared by the single-frame kernel and the ray-bank builder so that a frame's validation rays and its
+// training rays are the same bits.  (i, j) = the pixel's (column, row), no +0.5 centring (ray_utils.py:26); c2w: row-major
+// (3,4); r: origin | direction.
+__device__ __forceinline__ void ndc_pixel_ray(float fx, float fy, float cx, float cy, const float* c2w, float near,
+                                              float shift_near, float i, float j, float* r) {
+    const float dc[3] = {(i - cx) / fx, -(j - cy) / fy, -1.0f};
     float d[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) d[r] = dc[0] * a.c2w[4 * r + 0] + dc[1] * a.c2w[4 * r + 1] + dc[2] * a.c2w[4 * r + 2];
+    for (int k = 0; k < 3; ++k) d[k] = dc[0] * c2w[4 * k + 0] + dc[1] * c2w[4 * k + 1] + dc[2] * c2w[4 * k + 2];
     const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) d[r] /= nrm;
-    float o[3] = {a.c2w[3], a.c2w[7], a.c2w[11]};
+    for (int k = 0; k < 3; ++k) d[k] /= nrm;
+    float o[3] = {c2w[3], c2w[7], c2w[11]};
     // shift the origin to the near plane, then project
-    const float t = -(a.shift_near + o[2]) / d[2];
+    const float t = -(shift_near + o[2]) / d[2];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = o[r] + t * d[r];
+    for (int k = 0; k < 3; ++k) o[k] = o[k] + t * d[k];
     const float ox_oz = o[0] / o[2], oy_oz = o[1] / o[2];
-    const float sx = -1.0f / (a.cx / a.fx), sy = -1.0f / (a.cy / a.fy);
-    const float o2 = 1.0f + 2.0f * a.near / o[2];
-    float* r = a.rays + idx * 6;
+    const float sx = -1.0f / (cx / fx), sy = -1.0f / (cy / fy);
+    const float o2 = 1.0f + 2.0f * near / o[2];
     r[0] = sx * ox_oz;
     r[1] = sy * oy_oz;
     r[2] = o2;
     r[3] = sx * (d[0] / d[2] - ox_oz);
     r[4] = sy * (d[1] / d[2] - oy_oz);
     r[5] = 1.0f - o2;
+}
+
+__global__ void frame_rays_kernel(const FrameRayArgs a) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= a.count) return;
+    float r[6];
+    const long long pix = a.first + idx;
+    ndc_pixel_ray(a.fx, a.fy, a.cx, a.cy, a.c2w, a.near, a.shift_near, (float)(pix % a.W), (float)(pix / a.W), r);
+    float* out = a.rays + idx * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) out[k] = r[k];
+}
+
+// ---------------------------------------------------------------------------------
+// The training split's ray records (reference datasets/monocular.py:136-184) of every frame in one launch: one thread per
+// pixel, blockIdx.y = frame.  A record is 64 B; a lane storing its own record would put 16 B into each of 64 different
+// 64-B lines per store instruction, so each wave passes its 64 records through 4 KB of LDS and stores them as four
+// contiguous 1-KB runs (consecutive lanes, consecutive 16 B): measured at about half the time of the per-lane stores for 100
+// frames of 512 x 288.  The LDS slots of a record are XOR-swizzled by (record / 4) % 4: 16 lanes
+// writing chunk k of 16 consecutive records then cover all 16 slots of a 256-B bank row.
+constexpr int REC_THREADS = 256;
+
+__global__ __launch_bounds__(REC_THREADS) void ray_records_kernel(const NsffRayRecordArgs a) {
+    const long long n = (long long)a.H * a.W;                        // < 2^31 (checked by the entry point)
+    const long long pix = (long long)blockIdx.x * REC_THREADS + threadIdx.x;
+    const int frame = a.first_frame + (int)blockIdx.y;
+    float4 q[4] = {};
+    if (pix < n) {
+        const float* tab = a.frame_table + (long long)frame * NSFF_FRAME_TABLE;
+        const unsigned row = (unsigned)pix / (unsigned)a.W, col = (unsigned)pix - row * (unsigned)a.W;
+        const float u = (float)col, v = (float)row;
+        float r[6];
+        ndc_pixel_ray(a.fx, a.fy, a.cx, a.cy, tab, a.near, tab[12], u, v, r);
+        const long long p = (long long)frame * n + pix;
+        float rgb[3];
+        if (a.image_u8) {                                            // ToTensor: a true division, not a reciprocal multiply
+            const uint8_t* s = static_cast<const uint8_t*>(a.images) + p * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rgb[c] = (float)s[c] / 255.0f;
+        } else {
+            const float* s = static_cast<const float*>(a.images) + p * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rgb[c] = s[c];
+        }
+        const float mask = a.mask_u8 ? (float)static_cast<const uint8_t*>(a.masks)[p] / 255.0f
+                                     : static_cast<const float*>(a.masks)[p];
+        float2 fw = {0.f, 0.f}, bw = {0.f, 0.f};                     // the last frame has no forward flow, the first no backward
+        if (a.flow_fw && frame < a.n_frames - 1) fw = reinterpret_cast<const float2*>(a.flow_fw)[p];
+        if (a.flow_bw && frame > 0) bw = reinterpret_cast<const float2*>(a.flow_bw)[p];
+        q[0] = make_float4(r[0], r[1], r[2], r[3]);
+        q[1] = make_float4(r[4], r[5], rgb[0], rgb[1]);
+        q[2] = make_float4(rgb[2], (float)frame, a.disps[p], mask);
+        q[3] = make_float4(u + fw.x, v + fw.y, u + bw.x, v + bw.y);
+    }
+    float4* out = reinterpret_cast<float4*>(a.records) + (long long)frame * n * 4;
+    __shared__ float4 s_rec[REC_THREADS * 4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float4* sw = s_rec + wave * 256;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sw[lane * 4 + (k ^ ((lane >> 2) & 3))] = q[k];
+    __syncthreads();
+    const long long pix0 = (long long)blockIdx.x * REC_THREADS + wave * 64;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int rec = k * 16 + (lane >> 2), c = lane & 3;
+        if (pix0 + rec < n) out[(pix0 + rec) * 4 + c] = sw[rec * 4 + (c ^ ((rec >> 2) & 3))];
+    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -914,6 +980,23 @@ int nsff_frame_rays(const float* K4_host, const float* c2w_host, int32_t H, int3
     for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host[i];
     a.W = W; a.near = near; a.shift_near = shift_near; a.first = first_pixel; a.count = n_pixels; a.rays = rays;
     hipLaunchKernelGGL(frame_rays_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return nsff_launch_status();
+}
+
+int nsff_ray_records(const NsffRayRecordArgs* args, void* stream) {
+    if (!args) return NSFF_ERR_NULL;
+    const NsffRayRecordArgs& a = *args;
+    if (a.n_frames < 0 || a.H < 1 || a.W < 1 || a.n_pixels != (int64_t)a.H * a.W) return NSFF_ERR_INVALID;
+    if (a.first_frame < 0 || a.frame_count < 0 || (int64_t)a.first_frame + a.frame_count > a.n_frames) return NSFF_ERR_INVALID;
+    if (a.frame_count > 65535 || a.n_pixels > 0x7fffffffLL) return NSFF_ERR_INVALID;
+    if (a.frame_count == 0) return NSFF_OK;
+    if (!a.images || !a.disps || !a.masks || !a.frame_table || !a.records) return NSFF_ERR_NULL;
+    if (((uintptr_t)a.records & 15) || (((uintptr_t)a.flow_fw | (uintptr_t)a.flow_bw) & 7) ||
+        (((uintptr_t)a.disps | (uintptr_t)a.frame_table) & 3) || (!a.image_u8 && ((uintptr_t)a.images & 3)) ||
+        (!a.mask_u8 && ((uintptr_t)a.masks & 3)))
+        return NSFF_ERR_ALIGN;
+    const dim3 grid((unsigned)((a.n_pixels + REC_THREADS - 1) / REC_THREADS), (unsigned)a.frame_count);
+    hipLaunchKernelGGL(ray_records_kernel, grid, dim3(REC_THREADS), 0, (hipStream_t)stream, a);
     return nsff_launch_status();
 }
 

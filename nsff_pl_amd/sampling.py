@@ -18,6 +18,9 @@ Deviations from the reference, on purpose: a frame whose weights sum to 0 or to 
 reference's ``np.random.choice`` raises); when the +-5 window leaves no frame (11 frames or fewer) the frame is drawn from all
 frames (the reference's ``np.random.choice([])`` raises); one ``last_t`` per bank, not one per DataLoader worker.
 ``state_dict`` carries the weights and ``tmp_rgb`` (the reference's TODO at monocular.py:235).
+
+``RayBank.from_frames`` builds the records themselves on the GPU from decoded frames, poses and flow (one launch,
+:mod:`nsff_pl_amd.frames`) and keeps the loss's ``Ks`` / ``Ps``; ``frame_sample`` is the validation split's full-frame sample.
 """
 import numpy as np
 import torch
@@ -52,10 +55,24 @@ class RayBank:
         self._cdf = None                                                 # fp64 CDF of `weights`, rebuilt when stale
         self.rng = np.random.default_rng(seed)
         self.last_t = -1
+        self.Ks = self.Ps = None                                         # set by from_frames (monocular.py:127-134)
+
+    @classmethod
+    def from_frames(cls, K, poses, images, disps, masks, flows_fw, flows_bw, img_wh, hard_sampling=False, seed=None):
+        """The bank of decoded frames (GPU tensors at the target resolution, see :func:`frames.build_records`): the records
+        come from one launch, and ``Ks`` (1,3,3) / ``Ps`` (1,F,3,4) are what the loss projects with, so
+        ``NSFFTrainer(..., Ks=bank.Ks, Ps=bank.Ps, ray_bank=bank)`` is the whole set-up."""
+        from . import frames
+        records = frames.build_records(K, poses, images, disps, masks, flows_fw, flows_bw)
+        bank = cls(records, img_wh, hard_sampling=hard_sampling, seed=seed)
+        Ks, Ps = frames.projection_matrices(K, poses)
+        bank.Ks, bank.Ps = Ks.to(records.device), Ps.to(records.device)
+        return bank
 
     def to(self, device):
-        for k in ("records", "rgb", "weights", "tmp_rgb"):
-            setattr(self, k, getattr(self, k).to(device))
+        for k in ("records", "rgb", "weights", "tmp_rgb", "Ks", "Ps"):
+            if getattr(self, k) is not None:
+                setattr(self, k, getattr(self, k).to(device))
         self._cdf = None
         return self
 
@@ -99,6 +116,13 @@ class RayBank:
         u = torch.rand(batch_size, device=dev, generator=generator)
         _lib.ray_draw(self.records, t, u, self._refresh_cdf() if self.hard_sampling else None, out)
         return out
+
+    def frame_sample(self, t):
+        """Frame t as the validation split hands it to ``validation_step`` (monocular.py:252-294): {'rays' (H*W,6),
+        'ts' (H*W) int64, 'rgbs' (H*W,3), 'disp' (H*W), 'mask' (H*W)}, read from the records."""
+        r = self.records[int(t)]
+        return {"rays": r[:, :6].contiguous(), "ts": r[:, 9].long(), "rgbs": r[:, 6:9].contiguous(),
+                "disp": r[:, 10].contiguous(), "mask": r[:, 11].contiguous()}
 
     @torch.no_grad()
     def record(self, batch, rgb_fine):

@@ -6,6 +6,8 @@
 Cases: one metrics.ssim call (full-frame mean); RayBank.update_weights() over 24 and 100 frames (one SSIM launch writing the
 weights + one fp64 CDF launch); one 1024-ray RayBank.sample() (torch.rand + one draw-and-gather launch).  Byte bounds: the SSIM
 pass reads gt + pred (2 x 12 B per pixel) and writes the 4-B weight per pixel; the CDF reads 4 B and writes 8 B per pixel.
+frames.build_records for 100 frames with uint8 images and masks (csrc/rays.hip::ray_records_kernel): the whole call (frame table
+upload + one launch) and the launch alone; it reads 3 + 4 + 1 + 16 B and writes 64 B per pixel.
 """
 import argparse
 import json
@@ -17,7 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from nsff_pl_amd import metrics  # noqa: E402
+from nsff_pl_amd import _lib, frames, metrics  # noqa: E402
 from nsff_pl_amd.sampling import RayBank  # noqa: E402
 
 HBM_PEAK = 8.0e12          # B/s (MI355X datasheet)
@@ -37,6 +39,24 @@ def time_us(fn, reps, warmup=5):
         times.append(a.elapsed_time(b) * 1e3)
     times.sort()
     return times[len(times) // 2]
+
+
+def bench_build_records(dev, g, W, H, reps, F=100):
+    K = [[400.0, 0, W / 2], [0, 400.0, H / 2], [0, 0, 1]]
+    poses = torch.eye(4)[:3].repeat(F, 1, 1)
+    poses[:, :, 3] = torch.rand(F, 3) * 0.2 - 0.1
+    images = torch.randint(0, 256, (F, H, W, 3), device=dev, generator=g, dtype=torch.uint8)
+    masks = torch.randint(0, 2, (F, H, W), device=dev, generator=g, dtype=torch.uint8) * 255
+    disps = torch.rand(F, H, W, device=dev, generator=g)
+    fw, bw = (torch.randn(F, H, W, 2, device=dev, generator=g) for _ in range(2))
+    rec = torch.empty(F, H * W, 16, device=dev)
+    table = frames.frame_table(poses, dev)
+    K4 = [K[0][0], K[1][1], K[0][2], K[1][2]]
+    launch = lambda: _lib.ray_records(K4, table, images, disps, masks, fw, bw, 1.0, 0, F, rec)
+    res = {f"build_records_F{F}_us": time_us(lambda: frames.build_records(K, poses, images, disps, masks, fw, bw, out=rec), reps),
+           f"ray_records_F{F}_launch_us": time_us(launch, reps)}
+    res[f"ray_records_F{F}_bound_us"] = F * H * W * (3 + 4 + 1 + 16 + 64) / HBM_PEAK * 1e6
+    return res
 
 
 def main():
@@ -63,6 +83,7 @@ def main():
             out["sample_1024_us"] = time_us(lambda: bank.sample(1024, generator=g), args.reps)
         del bank, rec
         torch.cuda.empty_cache()
+    out.update(bench_build_records(dev, g, W, H, args.reps))
     print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
 
 
