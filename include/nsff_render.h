@@ -758,6 +758,34 @@ typedef struct NsffSsimArgs {
 int64_t nsff_ssim_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
 int nsff_ssim(const NsffSsimArgs* args, void* stream);
 
+/* The per-frame finishing work of eval.py on n_frames rendered frames of H x W pixels (eval.py:113-118, 183-184, 213-214,
+ * 222-223, 230-240; utils/visualization.py:10-15; metrics.py:6-16).  Only rgb is required; every other pointer may be NULL and
+ * every output is written only when given.  Inputs: rgb (F, H*W, 3) fp32, the raw rgb_fine; gt (F, H*W, 3) fp32; valid (F, H*W)
+ * uint8, non-zero = the pixel counts (the caller passes mask == 0); depth (F, H*W) fp32; lut (256, 3) uint8.  Outputs:
+ *   rgb_clipped  (F, H*W, 3) fp32   clip(rgb, 0, 1) (a NaN stays a NaN);
+ *   rgb_u8       (F, H*W, 3) uint8  255 * clip(rgb, 0, 1) rounded to fp32, then truncated (astype(np.uint8)); NaN gives 0;
+ *   sums         (F, 3) fp64        sum of (gt - clip(rgb))^2 over all 3 H W values, the same over the valid pixels, and the
+ *                                   number of valid pixels (needs gt): squares in fp32, added in fp64 in an order that depends
+ *                                   on H * W only -- bit-reproducible, and the same for a frame alone or inside a batch;
+ *   depth_range  (F, 2) fp32        min and max of nan_to_num(depth): NaN counts as 0, +-inf as +-FLT_MAX (needs depth);
+ *   depth_u8     (F, H*W) uint8     255 * ((x - min) / (max - min + 1e-8f)) truncated, x = nan_to_num(depth), each step one
+ *                                   fp32 operation, with the frame's own range (needs depth_range as well);
+ *   depth_rgb_u8 (F, H*W, 3) uint8  lut[depth_u8] (needs lut and depth_range).
+ * Two launches on `stream` (the second only for the 8-bit depth), no synchronisation, no allocation: capturable.  sums and
+ * depth_range are combined from per-workgroup partials in `scratch`: nsff_frame_finish_scratch_bytes() bytes, 16-byte aligned,
+ * ZERO before its first use (every call returns its counter words to zero and rewrites the partials before it reads them, so the
+ * buffer serves call after call; one call at a time per scratch buffer).  n_frames <= 65535 and
+ * 1 <= H * W < 2^31; a missing image, an output without its input or nothing to compute is NSFF_ERR_INVALID, before any launch.
+ * fp32 arrays 16-byte and uint8 arrays 4-byte aligned take the wide path; less aligned ones are read element by element. */
+typedef struct NsffFrameFinishArgs {
+    int32_t n_frames, H, W, pad_;
+    const float* rgb;  const float* gt;  const uint8_t* valid;  const float* depth;  const uint8_t* lut;
+    float* rgb_clipped;  uint8_t* rgb_u8;  double* sums;  float* depth_range;  uint8_t* depth_u8;  uint8_t* depth_rgb_u8;
+    void* scratch;  int64_t scratch_bytes;
+} NsffFrameFinishArgs;
+int64_t nsff_frame_finish_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int nsff_frame_finish(const NsffFrameFinishArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

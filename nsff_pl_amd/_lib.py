@@ -168,6 +168,14 @@ class SsimArgs(C.Structure):
                 ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+_FINISH_PTRS = ["rgb", "gt", "valid", "depth", "lut", "rgb_clipped", "rgb_u8", "sums", "depth_range", "depth_u8", "depth_rgb_u8"]
+
+
+class FrameFinishArgs(C.Structure):
+    _fields_ = ([("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pad_", C.c_int32)]
+                + [(n, _fp) for n in _FINISH_PTRS] + [("scratch", _fp), ("scratch_bytes", C.c_int64)])
+
+
 RAY_RECORD = 16
 _DRAW_OUT = ["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
@@ -263,6 +271,8 @@ _SIGNATURES = {
     "nsff_mpi_composite": (C.c_int, [C.POINTER(MpiArgs), _fp]),
     "nsff_ssim_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_ssim": (C.c_int, [C.POINTER(SsimArgs), _fp]),
+    "nsff_frame_finish_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_frame_finish": (C.c_int, [C.POINTER(FrameFinishArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1050,6 +1060,40 @@ def ssim(gt, pred, mask=None, map=None, mean_map=None, sums=None, scratch=None):
             raise RuntimeError(f"ssim: an output / mask has {t.numel()} elements, expected {n}")
     with torch.cuda.device(gt.device):
         _check(load().nsff_ssim(C.byref(a), _stream()), "nsff_ssim")
+
+
+def frame_finish_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_frame_finish_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def frame_finish(rgb, gt=None, valid=None, depth=None, lut=None, rgb_clipped=None, rgb_u8=None, sums=None, depth_range=None,
+                 depth_u8=None, depth_rgb_u8=None, scratch=None):
+    """nsff_frame_finish on F frames: rgb / gt (F, H, W, 3) fp32, valid (F, H, W) bool / uint8, depth (F, H, W) fp32, lut (256, 3)
+    uint8 -> whichever of rgb_clipped (F, H, W, 3) fp32, rgb_u8 (F, H, W, 3) uint8, sums (F, 3) fp64, depth_range (F, 2) fp32,
+    depth_u8 (F, H, W) uint8 and depth_rgb_u8 (F, H, W, 3) uint8 are given.  scratch: uint8 tensor of
+    frame_finish_scratch_bytes() bytes, zero before its first use (a fresh zeroed one when None)."""
+    require_gpu_tensor(rgb, "frame_finish: rgb")
+    if rgb.dim() != 4 or rgb.shape[-1] != 3:
+        raise RuntimeError(f"frame_finish: need (F, H, W, 3) frames, got {tuple(rgb.shape)}")
+    F, H, W = (int(v) for v in rgb.shape[:3])
+    if valid is not None and valid.dtype == torch.bool:
+        valid = valid.view(torch.uint8)
+    if (sums is not None or depth_range is not None) and scratch is None:
+        scratch = torch.zeros(max(frame_finish_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=rgb.device)
+    given = dict(rgb=rgb, gt=gt, valid=valid, depth=depth, lut=lut, rgb_clipped=rgb_clipped, rgb_u8=rgb_u8, sums=sums,
+                 depth_range=depth_range, depth_u8=depth_u8, depth_rgb_u8=depth_rgb_u8)
+    dtypes = dict(rgb=torch.float32, gt=torch.float32, depth=torch.float32, rgb_clipped=torch.float32, sums=torch.float64,
+                  depth_range=torch.float32)
+    sizes = dict(rgb=F * H * W * 3, gt=F * H * W * 3, valid=F * H * W, depth=F * H * W, lut=768, rgb_clipped=F * H * W * 3,
+                 rgb_u8=F * H * W * 3, sums=F * 3, depth_range=F * 2, depth_u8=F * H * W, depth_rgb_u8=F * H * W * 3)
+    a = FrameFinishArgs(n_frames=F, H=H, W=W, scratch=_dptr(scratch, torch.uint8, "frame_finish: scratch"),
+                        scratch_bytes=0 if scratch is None else scratch.numel())
+    for name, t in given.items():
+        if t is not None and (t.numel() != sizes[name] or t.device != rgb.device):
+            raise RuntimeError(f"frame_finish: {name} has {t.numel()} elements on {t.device}, expected {sizes[name]} on {rgb.device}")
+        setattr(a, name, _dptr(t, dtypes.get(name, torch.uint8), f"frame_finish: {name}"))
+    with torch.cuda.device(rgb.device):
+        _check(load().nsff_frame_finish(C.byref(a), _stream()), "nsff_frame_finish")
 
 
 def cdf(weights, out):

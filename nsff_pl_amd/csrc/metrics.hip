@@ -22,7 +22,20 @@
 // nsff_ray_draw: one batch of the training dataset's __getitem__ (datasets/monocular.py:233-250) on the device: pixel
 // indices by inverse-CDF search (first i with cdf[i] > u * total: a zero-weight pixel is never drawn) or uniformly
 // (floor(u * n)), then the record columns gathered straight into the batch tensors.
+//
+// nsff_frame_finish: the per-frame finishing work of the reference's eval.py on F rendered frames -- clip(rgb, 0, 1), the 8-bit
+// image (255 * clip) truncated (eval.py:183-184, 213-214, 222-223), the squared-error sums of metrics.psnr over the whole frame
+// and over the valid pixels (metrics.py:6-16), and the normalised 8-bit depth of utils/visualization.py:10-15 with its colour
+// table lookup.  Two launches: frame_image_kernel streams the image once (and reduces the sums and the depth range),
+// frame_depth_kernel quantises the depth with the range the first one wrote.  A workgroup owns 1024 consecutive pixels OF ONE
+// FRAME (grid.y = frame) and a lane four consecutive ones, so which values a lane, a wave and a workgroup add depends on H * W
+// alone: a frame's sums are the same bits at any position of any batch.  Per-workgroup partials go to scratch and the frame's
+// last-arriving workgroup adds them in a fixed order, as ssim_kernel does.  A lane moves its four pixels as 16-byte loads and
+// dword stores where its first pixel's FLAT index (frame * H * W + pixel) is a multiple of four -- then every address is
+// aligned (48, 16, 12 and 4 bytes per four pixels) -- and element by element otherwise (frames whose base is not a multiple of
+// four pixels, i.e. odd H * W, and each frame's last partial quad).
 #include <hip/hip_runtime.h>
+#include <cfloat>
 #include <cstdint>
 #include <cmath>
 
@@ -246,6 +259,212 @@ __global__ __launch_bounds__(DRAW_THREADS) void ray_draw_kernel(NsffRayDrawArgs 
     if (a.rand_idx) a.rand_idx[b] = idx;
 }
 
+constexpr int FIN_THREADS = 256, FIN_PX = 4, FIN_BLOCK_PX = FIN_THREADS * FIN_PX;
+
+struct FinPartial { double s[3]; float mn, mx; };                 // one workgroup's share of a frame: four 8-byte words
+
+// np.nan_to_num of an fp32 value: NaN -> 0, +-inf -> +-FLT_MAX
+__device__ __forceinline__ float nan_to_num(float x) { return x != x ? 0.f : fminf(fmaxf(x, -FLT_MAX), FLT_MAX); }
+// torch.clip(x, 0, 1): a NaN stays a NaN
+__device__ __forceinline__ float clip01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+// astype(np.uint8) of a value in [0, 255]: truncation toward zero; a NaN (numpy: undefined) gives 0
+__device__ __forceinline__ uint32_t trunc_u8(float v) { return v == v ? (uint32_t)(int)fminf(fmaxf(v, 0.f), 255.f) : 0u; }
+
+template <int NB>
+__device__ __forceinline__ void store_bytes(uint8_t* dst, const uint32_t (&q)[NB], int n_bytes, bool vec) {
+    if (vec) {                                                    // all NB bytes, dst 4-byte aligned
+        uint32_t* o = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+        for (int w = 0; w < NB / 4; ++w) o[w] = q[4 * w] | (q[4 * w + 1] << 8) | (q[4 * w + 2] << 16) | (q[4 * w + 3] << 24);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+            if (i < n_bytes) dst[i] = (uint8_t)q[i];
+    }
+}
+
+__global__ __launch_bounds__(FIN_THREADS) void frame_image_kernel(NsffFrameFinishArgs a, int aligned,
+                                                                  unsigned* __restrict__ counters,
+                                                                  FinPartial* __restrict__ partials) {
+    __shared__ double s_sum[FIN_THREADS / 64][3];
+    __shared__ float s_mm[FIN_THREADS / 64][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t f = blockIdx.y, HW = (int64_t)a.H * a.W, base = f * HW;
+    const int64_t p0 = ((int64_t)blockIdx.x * FIN_THREADS + tid) * FIN_PX;      // first pixel of this lane, in its frame
+    const int n = (int)min((int64_t)FIN_PX, max(HW - p0, (int64_t)0));          // its pixels: 4, a ragged 1..3, or none
+    const bool vec = aligned && n == FIN_PX && ((base + p0) & 3) == 0;
+    const int64_t q0 = base + p0;                                               // flat pixel index
+
+    float r[3 * FIN_PX], g[3 * FIN_PX], d[FIN_PX];
+    uint32_t v[FIN_PX];
+#pragma unroll
+    for (int i = 0; i < 3 * FIN_PX; ++i) { r[i] = 0.f; g[i] = 0.f; }
+#pragma unroll
+    for (int k = 0; k < FIN_PX; ++k) { d[k] = 0.f; v[k] = 0u; }
+    if (vec) {
+        const float4* R = reinterpret_cast<const float4*>(a.rgb + q0 * 3);
+#pragma unroll
+        for (int w = 0; w < 3; ++w) { const float4 t = R[w]; r[4 * w] = t.x; r[4 * w + 1] = t.y; r[4 * w + 2] = t.z; r[4 * w + 3] = t.w; }
+        if (a.gt) {
+            const float4* G = reinterpret_cast<const float4*>(a.gt + q0 * 3);
+#pragma unroll
+            for (int w = 0; w < 3; ++w) { const float4 t = G[w]; g[4 * w] = t.x; g[4 * w + 1] = t.y; g[4 * w + 2] = t.z; g[4 * w + 3] = t.w; }
+        }
+        if (a.valid) {
+            const uint32_t t = *reinterpret_cast<const uint32_t*>(a.valid + q0);
+            v[0] = t & 255u; v[1] = (t >> 8) & 255u; v[2] = (t >> 16) & 255u; v[3] = t >> 24;
+        }
+        if (a.depth) { const float4 t = *reinterpret_cast<const float4*>(a.depth + q0); d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < FIN_PX; ++k) {
+            if (k >= n) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                r[3 * k + c] = a.rgb[(q0 + k) * 3 + c];
+                if (a.gt) g[3 * k + c] = a.gt[(q0 + k) * 3 + c];
+            }
+            if (a.valid) v[k] = a.valid[q0 + k];
+            if (a.depth) d[k] = a.depth[q0 + k];
+        }
+    }
+
+    double acc[3] = {0.0, 0.0, 0.0};                              // squared error, the same over valid pixels, valid pixels
+    float mn = INFINITY, mx = -INFINITY;
+    uint32_t q[3 * FIN_PX];
+#pragma unroll
+    for (int k = 0; k < FIN_PX; ++k) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float cl = clip01(r[3 * k + c]);
+            r[3 * k + c] = cl;
+            q[3 * k + c] = trunc_u8(255.f * cl);
+            if (k < n && a.gt) {
+                const float e = g[3 * k + c] - cl;
+                const double sq = (double)(e * e);                // the square in fp32 (torch), the sum in fp64
+                acc[0] += sq;
+                if (v[k]) acc[1] += sq;
+            }
+        }
+        if (k < n) {
+            if (v[k]) acc[2] += 1.0;
+            const float x = nan_to_num(d[k]);
+            mn = fminf(mn, x); mx = fmaxf(mx, x);
+        }
+    }
+    if (n > 0) {
+        if (a.rgb_clipped) {
+            float* o = a.rgb_clipped + q0 * 3;
+            if (vec) {
+                float4* O = reinterpret_cast<float4*>(o);
+#pragma unroll
+                for (int w = 0; w < 3; ++w) O[w] = make_float4(r[4 * w], r[4 * w + 1], r[4 * w + 2], r[4 * w + 3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 3 * FIN_PX; ++i)
+                    if (i < 3 * n) o[i] = r[i];
+            }
+        }
+        if (a.rgb_u8) store_bytes(a.rgb_u8 + q0 * 3, q, 3 * n, vec);
+    }
+    if (!a.sums && !a.depth_range) return;
+
+    // workgroup reduction in a fixed order: butterfly within each wave, then the four waves in order
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) acc[t] += __shfl_xor(acc[t], o);
+        mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o));
+    }
+    if (lane == 0) { s_sum[wave][0] = acc[0]; s_sum[wave][1] = acc[1]; s_sum[wave][2] = acc[2]; s_mm[wave][0] = mn; s_mm[wave][1] = mx; }
+    __syncthreads();
+    if (wave != 0) return;
+    const int64_t n_blocks = gridDim.x;
+    FinPartial* fp = partials + f * n_blocks;
+    unsigned ticket = 0;
+    if (lane == 0) {
+        FinPartial mine;
+        for (int t = 0; t < 3; ++t) mine.s[t] = ((s_sum[0][t] + s_sum[1][t]) + s_sum[2][t]) + s_sum[3][t];
+        mine.mn = fminf(fminf(s_mm[0][0], s_mm[1][0]), fminf(s_mm[2][0], s_mm[3][0]));
+        mine.mx = fmaxf(fmaxf(s_mm[0][1], s_mm[1][1]), fmaxf(s_mm[2][1], s_mm[3][1]));
+        // publish the partial, then take a ticket (the frame's workgroups may run on any XCD).  The four 8-byte words go out as
+        // agent-scope atomic stores -- write-through, so no release fence: a fence per workgroup writes back every dirty line of
+        // its L2, the image being stored included, and 14 400 of them took 0.9 of the 1.0 ms a 100-frame call then cost
+        unsigned long long* slot = reinterpret_cast<unsigned long long*>(fp + blockIdx.x);
+        for (int t = 0; t < 3; ++t) __hip_atomic_store(slot + t, (unsigned long long)__double_as_longlong(mine.s[t]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(slot + 3, (unsigned long long)__float_as_uint(mine.mn) | ((unsigned long long)__float_as_uint(mine.mx) << 32),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ticket = __hip_atomic_fetch_add(counters + f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    ticket = __shfl(ticket, 0);
+    if (ticket != (unsigned)(n_blocks - 1)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    double tot[3] = {0.0, 0.0, 0.0};
+    mn = INFINITY; mx = -INFINITY;
+    for (int64_t t = lane; t < n_blocks; t += 64) {               // lane l adds blocks l, l + 64, ... in order
+        const volatile FinPartial* p = fp + t;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tot[k] += p->s[k];
+        mn = fminf(mn, p->mn); mx = fmaxf(mx, p->mx);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tot[k] += __shfl_xor(tot[k], o);
+        mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o));
+    }
+    if (lane == 0) {
+        if (a.sums) { a.sums[f * 3 + 0] = tot[0]; a.sums[f * 3 + 1] = tot[1]; a.sums[f * 3 + 2] = tot[2]; }
+        if (a.depth_range) { a.depth_range[f * 2 + 0] = mn; a.depth_range[f * 2 + 1] = mx; }
+        __hip_atomic_store(counters + f, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+    }
+}
+
+// visualize_depth (utils/visualization.py:10-15) with the frame's own range: every step one fp32 operation, as numpy rounds it
+__global__ __launch_bounds__(FIN_THREADS) void frame_depth_kernel(NsffFrameFinishArgs a, int aligned) {
+    __shared__ uint8_t s_lut[768];
+    const int tid = threadIdx.x;
+    if (a.depth_rgb_u8) {
+        for (int i = tid; i < 768; i += FIN_THREADS) s_lut[i] = a.lut[i];
+        __syncthreads();
+    }
+    const int64_t f = blockIdx.y, HW = (int64_t)a.H * a.W;
+    const int64_t p0 = ((int64_t)blockIdx.x * FIN_THREADS + tid) * FIN_PX;
+    const int n = (int)min((int64_t)FIN_PX, max(HW - p0, (int64_t)0));
+    if (n == 0) return;
+    const int64_t q0 = f * HW + p0;
+    const bool vec = aligned && n == FIN_PX && (q0 & 3) == 0;
+    const float mi = a.depth_range[f * 2], ma = a.depth_range[f * 2 + 1];
+    const float span = (ma - mi) + 1e-8f;
+    float d[FIN_PX] = {0.f, 0.f, 0.f, 0.f};
+    if (vec) {
+        const float4 t = *reinterpret_cast<const float4*>(a.depth + q0);
+        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < FIN_PX; ++k)
+            if (k < n) d[k] = a.depth[q0 + k];
+    }
+    uint32_t idx[FIN_PX], col[3 * FIN_PX];
+#pragma unroll
+    for (int k = 0; k < FIN_PX; ++k) {
+        const float x = (nan_to_num(d[k]) - mi) / span;            // IEEE division
+        idx[k] = trunc_u8(255.f * x);
+    }
+    if (a.depth_u8) store_bytes(a.depth_u8 + q0, idx, n, vec);
+    if (a.depth_rgb_u8) {
+#pragma unroll
+        for (int k = 0; k < FIN_PX; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) col[3 * k + c] = s_lut[idx[k] * 3 + c];
+        store_bytes(a.depth_rgb_u8 + q0 * 3, col, 3 * n, vec);
+    }
+}
+
+inline int64_t fin_blocks(int64_t n_pixels) { return (n_pixels + FIN_BLOCK_PX - 1) / FIN_BLOCK_PX; }
+
 inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 inline int64_t host_tiles(int32_t H, int32_t W) { return (int64_t)((W + TW - 1) / TW) * ((H + TH - 1) / TH); }
 
@@ -271,6 +490,39 @@ extern "C" int nsff_ssim(const NsffSsimArgs* a, void* stream) {
     const dim3 grid((a->W + TW - 1) / TW, (a->H + TH - 1) / TH, a->n_frames);
     hipLaunchKernelGGL(ssim_kernel, grid, dim3(SSIM_THREADS), 0, (hipStream_t)stream, a->gt, a->pred, a->mask, a->H, a->W,
                        a->map, a->mean_map, a->sums, counters, partials);
+    return nsff_launch_status();
+}
+
+extern "C" int64_t nsff_frame_finish_scratch_bytes(int32_t n_frames, int32_t H, int32_t W) {
+    if (n_frames < 1 || H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff) return 0;
+    return align16(4 * (int64_t)n_frames) + (int64_t)sizeof(FinPartial) * n_frames * fin_blocks((int64_t)H * W);
+}
+
+extern "C" int nsff_frame_finish(const NsffFrameFinishArgs* a, void* stream) {
+    if (!a) return NSFF_ERR_NULL;
+    if (!a->rgb) return NSFF_ERR_INVALID;                                        // no image: nothing to finish
+    if (a->n_frames < 1 || a->n_frames > 65535 || a->H < 1 || a->W < 1 || (int64_t)a->H * a->W > 0x7fffffff) return NSFF_ERR_INVALID;
+    const bool depth_out = a->depth_u8 || a->depth_rgb_u8;
+    if (a->depth_rgb_u8 && !a->lut) return NSFF_ERR_INVALID;                     // a colour image needs the colour table
+    if ((a->sums && !a->gt) || ((a->depth_range || depth_out) && !a->depth)) return NSFF_ERR_INVALID;
+    if (depth_out && !a->depth_range) return NSFF_ERR_INVALID;                   // the second launch reads the range there
+    const bool reduce = a->sums || a->depth_range;
+    if (!a->rgb_clipped && !a->rgb_u8 && !reduce) return NSFF_ERR_INVALID;       // nothing to compute
+    if (reduce && !a->scratch) return NSFF_ERR_NULL;
+    if (reduce && a->scratch_bytes < nsff_frame_finish_scratch_bytes(a->n_frames, a->H, a->W)) return NSFF_ERR_INVALID;
+    if (((uintptr_t)a->scratch & 15) || ((uintptr_t)a->sums & 7)) return NSFF_ERR_ALIGN;
+    if (((uintptr_t)a->rgb | (uintptr_t)a->gt | (uintptr_t)a->depth | (uintptr_t)a->rgb_clipped | (uintptr_t)a->depth_range) & 3)
+        return NSFF_ERR_ALIGN;
+    // the 16-byte / dword path needs every array it touches that way aligned; otherwise every lane goes element by element
+    const uintptr_t wide = (uintptr_t)a->rgb | (uintptr_t)a->gt | (uintptr_t)a->depth | (uintptr_t)a->rgb_clipped;
+    const uintptr_t narrow = (uintptr_t)a->valid | (uintptr_t)a->rgb_u8 | (uintptr_t)a->depth_u8 | (uintptr_t)a->depth_rgb_u8;
+    const int aligned = !(wide & 15) && !(narrow & 3);
+    unsigned* counters = reinterpret_cast<unsigned*>(a->scratch);
+    FinPartial* partials = a->scratch ? reinterpret_cast<FinPartial*>(reinterpret_cast<char*>(a->scratch) + align16(4 * (int64_t)a->n_frames))
+                                      : nullptr;
+    const dim3 grid((unsigned)fin_blocks((int64_t)a->H * a->W), a->n_frames);
+    hipLaunchKernelGGL(frame_image_kernel, grid, dim3(FIN_THREADS), 0, (hipStream_t)stream, *a, aligned, counters, partials);
+    if (depth_out) hipLaunchKernelGGL(frame_depth_kernel, grid, dim3(FIN_THREADS), 0, (hipStream_t)stream, *a, aligned);
     return nsff_launch_status();
 }
 

@@ -14,7 +14,15 @@ and PSNR -- the renderer-side pieces of the reference's ``eval.py`` / ``datasets
                            with one pixel all-gather (:mod:`nsff_pl_amd.dist`).
 * :func:`psnr`          -- metrics.py:6-16.
 * :func:`ssim`          -- metrics.py:19-33 (the reference's SSIM scale, see :mod:`nsff_pl_amd.metrics`).
+* :func:`render_split`  -- ``python eval.py --split ...`` for ``test``, ``test_spiral``, ``test_spiral{X}`` and
+                           ``test_fixview{X}_interp{Y}``: the split's camera path and times (:mod:`nsff_pl_amd.paths`), rays per
+                           pose on demand, :func:`render_sequence`, and the 8-bit frames eval.py writes (eval.py:183-184, 213-214,
+                           222-223; the depth image of ``save_depth``) finished on the GPU (``nsff_frame_finish``).
+* :class:`SequenceScores`, :func:`evaluate_split` -- the PSNR / SSIM table of split ``test`` (eval.py:173-176, 230-255).
 """
+import os
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -49,10 +57,10 @@ class PinnedPool:
     (``depth=2``: frames t and t+1 of a time interpolation can be held together).  Before a set is written again the pool
     waits for the copies of the frame that last used it, so ``sync=False`` frames never race each other."""
 
-    def __init__(self, depth=2):
+    def __init__(self, depth=2, dtype=torch.float32):
         if depth < 1:
             raise ValueError("PinnedPool depth must be >= 1")
-        self.depth, self._turn = int(depth), 0
+        self.depth, self._turn, self.dtype = int(depth), 0, dtype
         self._sets = [dict() for _ in range(self.depth)]     # slot -> {(key, shape): tensor}
         self._last = [None] * self.depth                     # slot -> the HostFrame that was handed this set
 
@@ -69,7 +77,7 @@ class PinnedPool:
         ck = (key, tuple(shape))
         bufs = self._sets[slot]
         if ck not in bufs:
-            bufs[ck] = torch.empty(*shape, dtype=torch.float32, pin_memory=True)
+            bufs[ck] = torch.empty(*shape, dtype=self.dtype, pin_memory=True)
         return bufs[ck]
 
 
@@ -255,3 +263,184 @@ def ssim(image_pred, image_gt, valid_mask=None, reduction='mean'):
     (pred, gt) argument order: one HIP launch, see :func:`nsff_pl_amd.metrics.ssim`."""
     from . import metrics
     return metrics.ssim(image_gt, image_pred, valid_mask=valid_mask, reduction=reduction)
+
+
+class SplitSamples:
+    """The samples of a test split as the reference's dataset yields them (monocular.py:256-278), made on demand: item i holds
+    the NDC rays of pose i (one ``nsff_frame_rays`` launch), its time index for every ray and the pose -- never more than the
+    frame being rendered."""
+
+    def __init__(self, K, poses_test, ts, img_wh, device):
+        self.K, self.poses, self.ts, self.img_wh, self.device = K, poses_test, ts, img_wh, device
+
+    def __len__(self):
+        return len(self.poses)
+
+    def __getitem__(self, i):
+        if not 0 <= i < len(self.poses):
+            raise IndexError(i)
+        w, h = self.img_wh
+        c2w = torch.as_tensor(self.poses[i], dtype=torch.float32)
+        return {'rays': frame_rays(self.K, c2w, h, w, device=self.device),
+                'ts': torch.full((h * w,), int(self.ts[i]), dtype=torch.long, device=self.device), 'c2w': c2w}
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+
+def _split_frames(models, embeddings, K, poses, split, img_wh, N_samples, N_importance, chunk, kwargs):
+    """(names, generator of render_sequence's (name, rgb, depth)) of a split; eval.py:134-141 for the flow outputs."""
+    from . import paths
+    poses_test, ts, interp = paths.split_path(poses, split)
+    device = next(next(iter(models.values())).parameters()).device
+    K = torch.as_tensor(np.asarray(K, dtype=np.float64) if not torch.is_tensor(K) else K, dtype=torch.float32).cpu()
+    kw = dict(kwargs)
+    if interp > 0:
+        kw['output_transient'] = True
+        kw['output_transient_flow'] = ['fw', 'bw']
+    samples = SplitSamples(K, poses_test, ts, img_wh, device)
+    frames = render_sequence(models, embeddings, samples, len(poses) - 1, N_samples, N_importance, img_wh, chunk=chunk,
+                             interp=interp, K=K, **kw)
+    return paths.frame_names(len(poses_test), interp), frames
+
+
+def render_split(models, embeddings, K, poses, split, img_wh, N_samples, N_importance, chunk=1024 * 32, depth=False, lut=None,
+                 to_host=False, **kwargs):
+    """``python eval.py --split SPLIT`` as a generator of ``(name, rgb_u8 (h,w,3) uint8, depth image or None)``.
+
+    K (3,3) intrinsics, poses (N,3,4) the dataset's poses (max_t = N - 1), split one of ``test``, ``test_spiral``,
+    ``test_spiral{X}``, ``test_fixview{X}_interp{Y}`` (:func:`nsff_pl_amd.paths.split_path`; Y > 0 turns on the transient and
+    flow outputs, eval.py:136-138).  Names and frame count are eval.py's: ``'{i:03d}'``, or ``'{i:03d}_{int(dt*100):03d}'`` with
+    ``(N-1) Y + 1`` frames.  rgb_u8 is ``(255 * clip(rgb_fine, 0, 1)).astype(uint8)``; with ``depth=True`` the third item is the
+    image of ``save_depth`` (eval.py:113-118): ``lut[index]`` (h,w,3) for a (256,3) uint8 colour table ``lut`` (what
+    ``cv2.applyColorMap`` looks up), the index image (h,w) without one.  Frames are GPU tensors; ``to_host=True`` yields
+    page-locked host tensors instead, copied on the copy stream while the next frame renders (a yielded frame stays valid
+    until two further frames have been taken from the generator)."""
+    from . import metrics
+    w, h = img_wh
+    names, frames = _split_frames(models, embeddings, K, poses, split, img_wh, N_samples, N_importance, chunk, kwargs)
+    pool = PinnedPool(depth=4, dtype=torch.uint8) if to_host else None
+    scratch, pending = None, None
+
+    def land(item):
+        name, host = item
+        host.wait()
+        return name, host['rgb_u8'], host.get('depth')
+    for name, (_, rgb, dep) in zip(names, frames):
+        if scratch is None and depth:
+            scratch = torch.zeros(_lib.frame_finish_scratch_bytes(1, h, w), dtype=torch.uint8, device=rgb.device)
+        out = metrics.finish_frames(rgb.reshape(1, h, w, 3), depth=dep.reshape(1, h, w) if depth else None, lut=lut,
+                                    scratch=scratch)
+        img = out['rgb_u8'][0]
+        dimg = (out['depth_rgb_u8'][0] if 'depth_rgb_u8' in out else out['depth_u8'][0]) if depth else None
+        if pool is None:
+            yield name, img, dimg
+            continue
+        dev = img.device
+        if dev not in _COPY_STREAM:
+            _COPY_STREAM[dev] = torch.cuda.Stream(device=dev)
+        copy_stream = _COPY_STREAM[dev]
+        slot = pool.next_slot()
+        host = HostFrame()
+        done = torch.cuda.Event()
+        done.record()                                         # this frame's finishing launches, on the render stream
+        with torch.cuda.stream(copy_stream):
+            copy_stream.wait_event(done)
+            for key, t in (('rgb_u8', img), ('depth', dimg)):
+                if t is not None:
+                    host[key] = pool.buffer(slot, key, tuple(t.shape))
+                    host[key].copy_(t, non_blocking=True)
+                    t.record_stream(copy_stream)
+            host.event = torch.cuda.Event()
+            host.event.record(copy_stream)
+        pool._last[slot] = host
+        if pending is not None:
+            yield land(pending)                               # frame i - 1: its copy ran beside this frame's render
+        pending = (name, host)
+    if pending is not None:
+        yield land(pending)
+
+
+class SequenceScores:
+    """The score arrays of eval.py's split ``test`` (:173-176, 230-255): PSNR and SSIM per frame over the whole image (column 0)
+    and over ``mask == 0`` (column 1; 0 for a frame scored without a mask, NaN for a mask that leaves no pixel).  ``add`` runs
+    one ``nsff_frame_finish`` and one ``nsff_ssim`` call per frame and keeps the values on the GPU; nothing is read back before
+    ``psnrs`` / ``ssims`` are asked for."""
+
+    def __init__(self):
+        self._rows = []                                        # per frame: (4,) fp32 GPU tensor [psnr, psnr_m, ssim, ssim_m]
+        self._scratch = {}
+        self.last = None                                       # finish_frames' outputs of the last frame added
+
+    def add(self, img_gt, rgb, mask=None):
+        """img_gt (h,w,3) fp32, rgb (h,w,3) fp32 (raw or clipped), mask (h,w) or None -- non-zero marks the dynamic pixels that
+        column 1 leaves out (eval.py:237-239 passes ``mask == 0``)."""
+        from . import metrics
+        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        gt = img_gt.reshape(1, h, w, 3).contiguous()
+        valid = None if mask is None else (mask.reshape(1, h, w) == 0)
+        key = (rgb.device, h, w)
+        if key not in self._scratch:
+            self._scratch[key] = torch.zeros(_lib.frame_finish_scratch_bytes(1, h, w), dtype=torch.uint8, device=rgb.device)
+        out = metrics.finish_frames(rgb.reshape(1, h, w, 3), gt=gt, valid_mask=valid, scratch=self._scratch[key])
+        p, pm = metrics.psnr_from_sums(out['sums'], h * w)
+        _, s, sm = metrics.ssim_maps(gt, out['rgb_clipped'], valid)
+        zero = torch.zeros_like(p)
+        self._rows.append(torch.cat([p, zero if mask is None else pm, s, zero if mask is None else sm]))
+        self.last = out
+        return out
+
+    def __len__(self):
+        return len(self._rows)
+
+    def _table(self):
+        if not self._rows:
+            return np.zeros((0, 4))
+        return torch.stack(self._rows).double().cpu().numpy()
+
+    @property
+    def psnrs(self):
+        return self._table()[:, 0:2]
+
+    @property
+    def ssims(self):
+        return self._table()[:, 2:4]
+
+    def means(self):
+        """(mean_psnr (2,), mean_ssim (2,)): np.nanmean over the frames (eval.py:243-244)."""
+        return np.nanmean(self.psnrs, 0), np.nanmean(self.ssims, 0)
+
+    def table(self):
+        """The lines eval.py:251-254 prints."""
+        return format_scores(*self.means())
+
+    def save(self, dir_name):
+        os.makedirs(dir_name, exist_ok=True)
+        np.save(os.path.join(dir_name, 'psnr.npy'), self.psnrs)
+        np.save(os.path.join(dir_name, 'ssim.npy'), self.ssims)
+
+
+def format_scores(mean_psnr, mean_ssim):
+    """eval.py:251-254 (without the LPIPS row): header, rule, PSNR row, SSIM row -- a list of lines."""
+    return ['Score \t Whole image  \t Dynamic only',
+            '-------------------------------------',
+            f'PSNR  \t {mean_psnr[0]:.4f} \t {mean_psnr[1]:.4f}',
+            f'SSIM  \t {mean_ssim[0]:.4f} \t {mean_ssim[1]:.4f}']
+
+
+def evaluate_split(models, embeddings, K, poses, img_wh, N_samples, N_importance, images_gt, masks=None, chunk=1024 * 32,
+                   sink=None, **kwargs):
+    """Render split ``test`` and score it against the ground truth in one loop (eval.py:181-240): images_gt (N,h,w,3) fp32 GPU
+    frames (or a sequence of them), masks (N,h,w) or None.  ``sink(name, rgb_u8)`` receives every 8-bit frame (a GPU tensor of
+    the frame just scored) when given.  Returns the :class:`SequenceScores`."""
+    if len(images_gt) != len(poses) or (masks is not None and len(masks) != len(poses)):
+        raise ValueError(f"evaluate_split: {len(poses)} poses need as many ground-truth frames"
+                         f"{'' if masks is None else ' and masks'}, got {len(images_gt)}"
+                         f"{'' if masks is None else ' and ' + str(len(masks))}")
+    names, frames = _split_frames(models, embeddings, K, poses, 'test', img_wh, N_samples, N_importance, chunk, kwargs)
+    scores = SequenceScores()
+    for i, (name, (_, rgb, _)) in enumerate(zip(names, frames)):
+        out = scores.add(images_gt[i], rgb, None if masks is None else masks[i])
+        if sink is not None:
+            sink(name, out['rgb_u8'][0])
+    return scores

@@ -7,6 +7,11 @@ and returns ``1 - loss``, i.e. ``(1 + ssim) / 2`` wherever ssim >= -1 (so 0.5 wh
 numbers of BASELINE.md (0.9672 full frame, 0.9321 inside the dynamic mask) are on this scale.  The map, its reductions and
 the channel-mean map of hard sampling come from one HIP launch (``nsff_ssim``, csrc/metrics.hip); there is no CPU path.
 LPIPS (metrics.py:36-51) needs AlexNet weights and is not provided.
+
+``finish_frames`` / ``psnr_frames`` are the per-frame finishing work of the reference's eval.py for F frames at once
+(``nsff_frame_finish``, csrc/metrics.hip): the clipped image, the 8-bit image eval.py writes, the squared-error sums behind
+``metrics.psnr`` over the whole frame and over a mask, and the normalised 8-bit depth of ``utils/visualization.visualize_depth``
+-- no boolean indexing, no host synchronisation.
 """
 import torch
 
@@ -80,3 +85,68 @@ def ssim_maps(gt, pred, valid_mask=None, window_size=11):
     frame = (1 - sums[:, 0] / (3 * H * W)).float()
     frame_mask = None if mask is None else (1 - sums[:, 1] / (3 * sums[:, 2])).float()
     return 1 - loss, frame, frame_mask
+
+
+def _frames4(t, what, last):
+    if t.dim() != 4 or t.shape[-1] != last:
+        raise RuntimeError(f"{what}: need (F, H, W, {last}) frames, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def finish_frames(rgb, gt=None, valid_mask=None, depth=None, lut=None, images=True, scratch=None):
+    """eval.py's finishing work on F frames in one ``nsff_frame_finish`` call (two launches, no host sync).
+
+    rgb (F, H, W, 3) fp32, the raw ``rgb_fine``; gt (F, H, W, 3) fp32; valid_mask (F, H, W) bool / uint8, non-zero = the pixel
+    counts (eval.py passes ``mask == 0``); depth (F, H, W) fp32; lut (256, 3) uint8, the colour table that stands for
+    ``cv2.applyColorMap``.  Returns a dict of GPU tensors:
+
+    * ``rgb_clipped`` (F, H, W, 3) fp32 and ``rgb_u8`` (F, H, W, 3) uint8 = ``(255 * clip(rgb, 0, 1)).astype(uint8)`` (eval.py:222-223)
+      -- unless ``images=False``;
+    * with gt: ``sums`` (F, 3) fp64 = [sum of (gt - clip(rgb))**2, the same over the valid pixels, valid pixels] (see
+      :func:`psnr_from_sums`);
+    * with depth: ``depth_range`` (F, 2) fp32, min and max of ``nan_to_num(depth)`` per frame, and ``depth_u8`` (F, H, W) uint8, the
+      index image of ``visualize_depth``; with lut as well ``depth_rgb_u8`` (F, H, W, 3) uint8 = ``lut[depth_u8]``.
+
+    scratch: a zeroed uint8 tensor of ``_lib.frame_finish_scratch_bytes(F, H, W)`` bytes that callers in a loop may keep."""
+    rgb = _frames4(rgb, "finish_frames: rgb", 3)
+    F, H, W = (int(v) for v in rgb.shape[:3])
+    dev = rgb.device
+    out = {}
+    if images:
+        out["rgb_clipped"] = torch.empty_like(rgb)
+        out["rgb_u8"] = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    if gt is not None:
+        gt = _frames4(gt, "finish_frames: gt", 3)
+        out["sums"] = torch.empty(F, 3, dtype=torch.float64, device=dev)
+    elif valid_mask is not None:
+        raise ValueError("finish_frames: valid_mask selects the pixels of the error sums and needs gt")
+    if valid_mask is not None:
+        valid_mask = valid_mask.reshape(F, H, W)
+        valid_mask = (valid_mask if valid_mask.dtype in (torch.bool, torch.uint8) else valid_mask != 0).contiguous()
+    if depth is not None:
+        depth = depth.reshape(F, H, W).contiguous()
+        out["depth_range"] = torch.empty(F, 2, dtype=torch.float32, device=dev)
+        out["depth_u8"] = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+        if lut is not None:
+            lut = torch.as_tensor(lut).to(device=dev, dtype=torch.uint8).reshape(256, 3).contiguous()
+            out["depth_rgb_u8"] = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    if not out:
+        raise ValueError("finish_frames: nothing to compute (images=False without gt or depth)")
+    _lib.frame_finish(rgb, gt=gt, valid=valid_mask, depth=depth, lut=lut if "depth_rgb_u8" in out else None, scratch=scratch, **out)
+    return out
+
+
+def psnr_from_sums(sums, n_pixels):
+    """``(psnr (F,), psnr_valid (F,))`` fp32 from the ``sums`` of :func:`finish_frames`: ``-10 log10(sum / count)`` in fp64 with
+    ``count = 3 * n_pixels`` and ``3 * valid pixels``; NaN where a frame has no valid pixel (the reference's ``mean()`` of an empty
+    selection)."""
+    whole = -10 * torch.log10(sums[:, 0] / (3 * n_pixels))
+    valid = -10 * torch.log10(sums[:, 1] / (3 * sums[:, 2]))
+    return whole.float(), valid.float()
+
+
+def psnr_frames(gt, rgb, valid_mask=None):
+    """metrics.psnr(gt, clip(rgb, 0, 1)) of F frames -- over the whole frame and over valid_mask -- from one pass over the images:
+    ``(psnr (F,), psnr_valid (F,))`` fp32 on the GPU; psnr_valid is NaN for a frame without a valid pixel (and without a mask)."""
+    out = finish_frames(rgb, gt=gt, valid_mask=valid_mask, images=False)
+    return psnr_from_sums(out["sums"], int(rgb.shape[1]) * int(rgb.shape[2]))

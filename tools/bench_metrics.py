@@ -8,6 +8,9 @@ weights + one fp64 CDF launch); one 1024-ray RayBank.sample() (torch.rand + one 
 pass reads gt + pred (2 x 12 B per pixel) and writes the 4-B weight per pixel; the CDF reads 4 B and writes 8 B per pixel.
 frames.build_records for 100 frames with uint8 images and masks (csrc/rays.hip::ray_records_kernel): the whole call (frame table
 upload + one launch) and the launch alone; it reads 3 + 4 + 1 + 16 B and writes 64 B per pixel.
+metrics.finish_frames on 1 and 100 frames with every input and output (csrc/metrics.hip::frame_image_kernel + frame_depth_kernel):
+the whole call (output allocation + two launches) and nsff_frame_finish alone on preallocated outputs.  The image pass reads
+12 + 12 + 1 + 4 B and writes 12 + 3 B per pixel, the depth pass reads 4 B and writes 1 + 3 B: 52 B per pixel.
 """
 import argparse
 import json
@@ -59,6 +62,23 @@ def bench_build_records(dev, g, W, H, reps, F=100):
     return res
 
 
+FINISH_BYTES_PER_PIXEL = (12 + 12 + 1 + 4) + (12 + 3) + 4 + (1 + 3)
+
+
+def bench_finish_frames(dev, g, W, H, reps, F):
+    rgb = torch.rand(F, H, W, 3, device=dev, generator=g) * 1.2 - 0.1
+    gt = torch.rand(F, H, W, 3, device=dev, generator=g)
+    valid = torch.rand(F, H, W, device=dev, generator=g) < 0.7
+    depth = torch.rand(F, H, W, device=dev, generator=g) * 4
+    lut = torch.randint(0, 256, (256, 3), device=dev, generator=g, dtype=torch.uint8)
+    outs = metrics.finish_frames(rgb, gt=gt, valid_mask=valid, depth=depth, lut=lut)
+    scratch = torch.zeros(_lib.frame_finish_scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    launch = lambda: _lib.frame_finish(rgb, gt=gt, valid=valid, depth=depth, lut=lut, scratch=scratch, **outs)
+    return {f"finish_frames_F{F}_us": time_us(lambda: metrics.finish_frames(rgb, gt=gt, valid_mask=valid, depth=depth, lut=lut), reps),
+            f"frame_finish_F{F}_launch_us": time_us(launch, reps),
+            f"frame_finish_F{F}_bound_us": F * H * W * FINISH_BYTES_PER_PIXEL / HBM_PEAK * 1e6}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
@@ -84,6 +104,9 @@ def main():
         del bank, rec
         torch.cuda.empty_cache()
     out.update(bench_build_records(dev, g, W, H, args.reps))
+    for F in (1, 100):
+        out.update(bench_finish_frames(dev, g, W, H, args.reps, F))
+        torch.cuda.empty_cache()
     print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
 
 
