@@ -786,6 +786,48 @@ typedef struct NsffFrameFinishArgs {
 int64_t nsff_frame_finish_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
 int nsff_frame_finish(const NsffFrameFinishArgs* args, void* stream);
 
+/* ---- induced optical flow of rendered frames: maps, end-point error, colour images (csrc/flow.hip).
+ * What the reference's test.ipynb does on the host with the test-time outputs xyz_fw / xyz_bw (rendering.py:280-287), for
+ * n_frames frames of H x W pixels and both directions (index 0 forward, 1 backward) in one call.  Three stages, selected by the
+ * pointers given, each callable alone:
+ *   projection   xyz[d] (F, H*W, 3) fp32 NDC points -> flow[d] (F, H*W, 2) fp32, pixels: the reference's ndc2world
+ *                (ray_utils.py:142-145, eps = 1e-6f), Ps[clamp(t + 1, max = max_t)] (fw) / Ps[clamp(t - 1, min = 0)] (bw) applied as
+ *                ((p0 X + p1 Y) + p2 Z) + p3 per row, uv = uvd.xy / (|uvd.z| + 1e-8f) (losses.py:99-111), minus the integer pixel
+ *                coordinates; every step one fp32 operation.  t = ts[frame] (int32, (F)); Ps (n_poses, 3, 4) fp32; fx, fy, cx, cy
+ *                the intrinsics.  A pixel is valid when uvd.z > 0 and t < max_t (fw) / t > 0 (bw) (losses.py:115-116; a NaN point
+ *                is not); an invalid pixel gets both components NSFF_FLOW_UNKNOWN (the Middlebury convention: |.| > 1e7 is unknown).
+ *                A row index outside 0 .. n_poses - 1 (a time outside the sequence) is clamped into it.
+ *   EPE          flow[d] (written by the projection, or the caller's own map where xyz[d] is NULL) against gt[d] (F, H*W, 2):
+ *                sqrtf(du^2 + dv^2) in fp32 over the pixels where both flows are known (|.| <= 1e7, not NaN) and the ground truth
+ *                is non-zero in a component (flowlib.flow_error's smallflow = 0 rule), added in fp64:
+ *                epe_sums (F, 2, 3) fp64 and epe_counts (F, 2, 3) int64 per frame and direction for [all, mask != 0, mask == 0]
+ *                (mask (F, H*W) uint8 or NULL: the last two stay 0).  A direction without a pair has zero sums and counts.
+ *                Fixed summation order that depends on H * W only: the same bits for a frame alone or in a batch.
+ *   colour       flowlib.flow_to_image / compute_color in fp32: image[d] (F, H*W, 3) uint8 of flow[d], gt_image[d] of gt[d].
+ *                Unknown and NaN pixels are zeroed before the radius and painted black.  The scale of frame f, direction d is
+ *                float(double(r) + 2^-52) with r = scale[f][d][c] where `scale` (F, 2, 2) fp32 is given, else maxrad[f][d][c];
+ *                c = 1 for a ground-truth image -- and for the map's image too when share_gt_scale != 0 -- else 0.
+ *   maxrad       (F, 2, 2) fp32 out: per frame and direction the maximum of sqrtf(u^2 + v^2) over the known pixels of [flow[d],
+ *                gt[d]] (0 where there is none); needed for colouring without `scale`.
+ * At most two launches on `stream`, no synchronisation, no allocation: capturable.  epe_* and maxrad are combined from
+ * per-workgroup partials in `scratch`: nsff_flow_maps_scratch_bytes() bytes, 16-byte aligned, ZERO before its first use (every
+ * call leaves its counter words zero; one call at a time per scratch buffer).  n_frames <= 65535, 1 <= H * W < 2^31,
+ * 0 <= max_t < n_poses; an output without its input, a ground truth without a map of its direction or nothing to compute is
+ * NSFF_ERR_INVALID, a missing Ps / ts / flow[d] beside points or a missing scratch NSFF_ERR_NULL -- all before any launch.
+ * flow / gt need 8-byte, every other fp32 / int32 array 4-byte alignment (NSFF_ERR_ALIGN). */
+#define NSFF_FLOW_UNKNOWN    1e10f
+typedef struct NsffFlowMapsArgs {
+    int32_t n_frames, H, W, n_poses, max_t, share_gt_scale;
+    float   fx, fy, cx, cy;
+    const float* xyz[2];  const float* Ps;  const int32_t* ts;
+    float* flow[2];  const float* gt[2];  const uint8_t* mask;
+    double* epe_sums;  int64_t* epe_counts;  float* maxrad;  const float* scale;
+    uint8_t* image[2];  uint8_t* gt_image[2];
+    void* scratch;  int64_t scratch_bytes;
+} NsffFlowMapsArgs;
+int64_t nsff_flow_maps_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int nsff_flow_maps(const NsffFlowMapsArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

@@ -14,7 +14,10 @@ from .rendering import render_rays, sample_pdf
 from .interpolation import interpolate
 from .frames import build_records, projection_matrices
 from .sampling import RayBank
+from . import flow
+from .flow import induced_flow, flow_to_image, flow_epe, epe_from_sums
 
 __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "set_precision", "get_precision",
            "set_range_check", "get_range_check", "range_flags", "RangeFlags",
-           "build_records", "projection_matrices", "RayBank"]
+           "build_records", "projection_matrices", "RayBank",
+           "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums"]

@@ -176,6 +176,17 @@ class FrameFinishArgs(C.Structure):
                 + [(n, _fp) for n in _FINISH_PTRS] + [("scratch", _fp), ("scratch_bytes", C.c_int64)])
 
 
+FLOW_UNKNOWN = 1e10            # NSFF_FLOW_UNKNOWN: both components of an induced-flow pixel without a valid projection
+
+
+class FlowMapsArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_poses", C.c_int32), ("max_t", C.c_int32),
+                ("share_gt_scale", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("xyz", _fp * 2), ("Ps", _fp), ("ts", _fp), ("flow", _fp * 2), ("gt", _fp * 2), ("mask", _fp),
+                ("epe_sums", _fp), ("epe_counts", _fp), ("maxrad", _fp), ("scale", _fp), ("image", _fp * 2), ("gt_image", _fp * 2),
+                ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
 RAY_RECORD = 16
 _DRAW_OUT = ["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
@@ -273,6 +284,8 @@ _SIGNATURES = {
     "nsff_ssim": (C.c_int, [C.POINTER(SsimArgs), _fp]),
     "nsff_frame_finish_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_frame_finish": (C.c_int, [C.POINTER(FrameFinishArgs), _fp]),
+    "nsff_flow_maps_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_flow_maps": (C.c_int, [C.POINTER(FlowMapsArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1094,6 +1107,63 @@ def frame_finish(rgb, gt=None, valid=None, depth=None, lut=None, rgb_clipped=Non
         setattr(a, name, _dptr(t, dtypes.get(name, torch.uint8), f"frame_finish: {name}"))
     with torch.cuda.device(rgb.device):
         _check(load().nsff_frame_finish(C.byref(a), _stream()), "nsff_frame_finish")
+
+
+def flow_maps_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_flow_maps_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def flow_maps(F, H, W, xyz=(None, None), K4=None, Ps=None, ts=None, max_t=0, flow=(None, None), gt=(None, None), mask=None,
+              epe_sums=None, epe_counts=None, maxrad=None, scale=None, share_gt_scale=False, image=(None, None),
+              gt_image=(None, None), scratch=None):
+    """nsff_flow_maps on F frames of H x W pixels; every pair is (forward, backward), either entry may be None.  xyz (F, H*W, 3)
+    fp32 NDC points -> flow (F, H, W, 2) fp32 with K4 = (fx, fy, cx, cy), Ps (N, 3, 4) fp32, ts (F,) int32, max_t; flow (written, or
+    the caller's own where xyz is None) against gt (F, H, W, 2) [and mask (F, H, W) bool / uint8] -> epe_sums (F, 2, 3) fp64 and
+    epe_counts (F, 2, 3) int64; maxrad (F, 2, 2) fp32 out; image / gt_image (F, H, W, 3) uint8 coloured on scale (F, 2, 2) fp32 or, without
+    one, on maxrad.  scratch: uint8 tensor of flow_maps_scratch_bytes() bytes, zero before its first use (a fresh one when None)."""
+    F, H, W = int(F), int(H), int(W)
+    n = F * H * W
+    a = FlowMapsArgs(n_frames=F, H=H, W=W, max_t=int(max_t), share_gt_scale=int(bool(share_gt_scale)))
+    if K4 is not None:
+        a.fx, a.fy, a.cx, a.cy = (float(v) for v in K4)
+    first = next((t for t in list(xyz) + list(flow) + list(gt) if t is not None), None)
+    require_gpu_tensor(first, "flow_maps: points / flow")
+    dev = first.device
+
+    def put(field, t, dtype, numel, what, index=None):
+        if t is None:
+            return
+        ptr = _dptr(t, dtype, f"flow_maps: {what}")
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"flow_maps: {what} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        if index is None:
+            setattr(a, field, ptr)
+        else:
+            getattr(a, field)[index] = ptr
+    for d, tag in enumerate(("fw", "bw")):
+        put("xyz", xyz[d], torch.float32, n * 3, f"xyz_{tag}", d)
+        put("flow", flow[d], torch.float32, n * 2, f"flow_{tag}", d)
+        put("gt", gt[d], torch.float32, n * 2, f"gt_{tag}", d)
+        put("image", image[d], torch.uint8, n * 3, f"image_{tag}", d)
+        put("gt_image", gt_image[d], torch.uint8, n * 3, f"gt_image_{tag}", d)
+    if Ps is not None:
+        a.n_poses = int(Ps.numel() // 12)
+        put("Ps", Ps, torch.float32, a.n_poses * 12, "Ps")
+    put("ts", ts, torch.int32, F, "ts")
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    put("mask", mask, torch.uint8, n, "mask")
+    put("epe_sums", epe_sums, torch.float64, F * 6, "epe_sums")
+    put("epe_counts", epe_counts, torch.int64, F * 6, "epe_counts")
+    put("maxrad", maxrad, torch.float32, F * 4, "maxrad")
+    put("scale", scale, torch.float32, F * 4, "scale")
+    if (epe_sums is not None or maxrad is not None) and scratch is None:
+        scratch = torch.zeros(max(flow_maps_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    if scratch is not None:
+        put("scratch", scratch, torch.uint8, scratch.numel(), "scratch")
+        a.scratch_bytes = scratch.numel()
+    with torch.cuda.device(dev):
+        _check(load().nsff_flow_maps(C.byref(a), _stream()), "nsff_flow_maps")
 
 
 def cdf(weights, out):

@@ -19,6 +19,8 @@ and PSNR -- the renderer-side pieces of the reference's ``eval.py`` / ``datasets
                            pose on demand, :func:`render_sequence`, and the 8-bit frames eval.py writes (eval.py:183-184, 213-214,
                            222-223; the depth image of ``save_depth``) finished on the GPU (``nsff_frame_finish``).
 * :class:`SequenceScores`, :func:`evaluate_split` -- the PSNR / SSIM table of split ``test`` (eval.py:173-176, 230-255).
+* :func:`flow_frames`, :class:`FlowScores` -- the flow panel of the reference's test.ipynb: the induced optical flow of every
+                           training pose, its colour image beside the dataset's flow, and the end-point error (``nsff_flow_maps``).
 """
 import os
 
@@ -444,3 +446,189 @@ def evaluate_split(models, embeddings, K, poses, img_wh, N_samples, N_importance
         if sink is not None:
             sink(name, out['rgb_u8'][0])
     return scores
+
+
+class FlowScores:
+    """End-point error of the induced flow per frame: ``epe`` (N, 2 directions [fw, bw], 3 selections [all, dynamic = mask != 0,
+    static = mask == 0]) in pixels, NaN where nothing was counted (no ground truth, an edge frame's missing neighbour, no mask).
+    ``add`` keeps the sums and counts of ``nsff_flow_maps`` on the GPU; nothing is read back before ``epe`` / ``counts`` are asked
+    for."""
+
+    def __init__(self):
+        self._sums, self._counts = [], []                      # per frame: (2, 3) fp64 / int64 GPU tensors
+
+    def add(self, sums, counts):
+        self._sums.append(sums.reshape(2, 3))
+        self._counts.append(counts.reshape(2, 3))
+
+    def __len__(self):
+        return len(self._sums)
+
+    @property
+    def counts(self):
+        if not self._counts:
+            return np.zeros((0, 2, 3), np.int64)
+        return torch.stack(self._counts).cpu().numpy()
+
+    @property
+    def epe(self):
+        if not self._sums:
+            return np.zeros((0, 2, 3))
+        from . import flow
+        return flow.epe_from_sums(torch.stack(self._sums), torch.stack(self._counts)).cpu().numpy()
+
+    def means(self):
+        """(2, 3): np.nanmean over the frames, per direction and selection (NaN where no frame has a value)."""
+        epe = self.epe
+        out = np.full((2, 3), np.nan)
+        if len(epe):
+            have = ~np.isnan(epe).all(0)
+            out[have] = np.nanmean(epe[:, have], 0)
+        return out
+
+    def table(self):
+        """Lines in the manner of :func:`format_scores`."""
+        m = self.means()
+        return ['EPE   \t Whole image  \t Dynamic only \t Static only',
+                '---------------------------------------------------',
+                f'fw    \t {m[0, 0]:.4f} \t {m[0, 1]:.4f} \t {m[0, 2]:.4f}',
+                f'bw    \t {m[1, 0]:.4f} \t {m[1, 1]:.4f} \t {m[1, 2]:.4f}']
+
+    def save(self, dir_name):
+        os.makedirs(dir_name, exist_ok=True)
+        np.save(os.path.join(dir_name, 'epe.npy'), self.epe)
+        np.save(os.path.join(dir_name, 'epe_counts.npy'), self.counts)
+
+
+class FlowFrames:
+    """What :func:`flow_frames` returns: an iterator of ``(name, maps)`` whose ``scores`` (:class:`FlowScores`) fill as it runs."""
+
+    def __init__(self, generator, scores):
+        self._generator, self.scores = generator, scores
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._generator)
+
+    def close(self):
+        self._generator.close()
+
+
+def flow_frames(models, embeddings, K, poses, img_wh, N_samples, N_importance, chunk=1024 * 32, frames=None, flows_fw=None,
+                flows_bw=None, masks=None, maxrad=None, to_host=False, **kwargs):
+    """The flow panel of the reference's test.ipynb for the training poses, on the GPU: an iterator of ``(name, maps)`` with a
+    ``scores`` attribute (:class:`FlowScores`).
+
+    K (3,3), poses (N,3,4) the dataset's poses (frame i is rendered from pose i at time i, max_t = N - 1); ``frames``: the pose
+    indices to do (default all).  Each frame is rendered with ``output_transient=True, output_transient_flow=['fw','bw']``, its
+    expected warped points ``xyz_fw`` / ``xyz_bw`` go through ``nsff_flow_maps`` (:mod:`nsff_pl_amd.flow`), and ``maps`` holds
+    ``flow_fw`` / ``flow_bw`` (h,w,2) fp32 -- :data:`nsff_pl_amd.flow.UNKNOWN` where a pixel has no valid projection, as in all of
+    frame N-1's forward and frame 0's backward map -- and their colour images ``flow_fw_u8`` / ``flow_bw_u8`` (h,w,3) uint8.
+    flows_fw / flows_bw (N,h,w,2) fp32 GPU tensors, the dataset's flow: ``gt_fw_u8`` / ``gt_bw_u8`` join them, prediction and ground
+    truth are coloured on the ground truth's largest radius, and the end-point error of every frame goes to ``scores`` -- over the
+    whole frame and, with masks (N,h,w; non-zero = dynamic), over the dynamic and the static pixels.  ``maxrad``: colour everything on
+    this radius instead.  Names are eval.py's ``'{i:03d}'``.  ``to_host=True`` yields page-locked host tensors instead, copied on the
+    copy stream while the next frame renders (a yielded frame stays valid until two further frames have been taken)."""
+    model = models['fine']
+    if not getattr(model, "has_flow_heads", False):
+        raise RuntimeError("flow_frames: models['fine'] has no scene-flow heads (NeRF(..., encode_transient=True, output_flow=True)): "
+                           "there are no warped points to project")
+    n = len(poses)
+    todo = list(range(n)) if frames is None else [int(i) for i in frames]
+    if any(not 0 <= i < n for i in todo):
+        raise ValueError(f"flow_frames: frames {todo} outside the sequence of {n} poses")
+    w, h = (int(v) for v in img_wh)
+    for t, what, last in ((flows_fw, "flows_fw", (h, w, 2)), (flows_bw, "flows_bw", (h, w, 2)), (masks, "masks", (h, w))):
+        if t is not None:
+            _lib.require_gpu_tensor(t, f"flow_frames: {what}")
+            if tuple(t.shape) != (n,) + last:
+                raise RuntimeError(f"flow_frames: {what} must be {(n,) + last}, got {tuple(t.shape)}")
+    if (flows_fw is None) != (flows_bw is None):
+        raise ValueError("flow_frames: flows_fw and flows_bw go together (a frame without a neighbour on one side has zero flow "
+                         "there, as in the ray records)")
+    scores = FlowScores()
+    return FlowFrames(_flow_frames(models, embeddings, K, poses, (w, h), N_samples, N_importance, chunk, todo, flows_fw, flows_bw,
+                                   masks, maxrad, to_host, scores, kwargs), scores)
+
+
+def _flow_frames(models, embeddings, K, poses, img_wh, N_samples, N_importance, chunk, todo, flows_fw, flows_bw, masks, maxrad,
+                 to_host, scores, kwargs):
+    from . import flow, paths
+    from . import frames as nframes
+    w, h = img_wh
+    n = len(poses)
+    device = next(models['fine'].parameters()).device
+    K = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)
+    K4 = (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+    Ps = nframes.projection_matrices(K, poses)[1][0].to(device).contiguous()
+    K = torch.as_tensor(K, dtype=torch.float32)
+    names = paths.frame_names(n)
+    kw = dict(kwargs, output_transient=True, output_transient_flow=['fw', 'bw'])
+    gts = (flows_fw, flows_bw)
+    have_gt = any(g is not None for g in gts)
+    scratch = torch.zeros(_lib.flow_maps_scratch_bytes(1, h, w), dtype=torch.uint8, device=device)
+    scale = None if maxrad is None else flow._scale(maxrad, 1, device, "flow_frames")
+    pools = (PinnedPool(depth=4), PinnedPool(depth=4, dtype=torch.uint8)) if to_host else None
+    pending = None
+
+    def land(item):
+        name, host = item
+        host.wait()
+        return name, dict(host)
+    for i in todo:
+        pose = torch.as_tensor(np.asarray(poses[i]), dtype=torch.float32)
+        rays = frame_rays(K, pose, h, w, device=device)
+        ts = torch.full((h * w,), i, dtype=torch.long, device=device)
+        res = render_frame(models, embeddings, rays, ts, n - 1, N_samples, N_importance, chunk, keys=('xyz_fw', 'xyz_bw'), **kw)
+        gt = tuple(None if g is None else g[i:i + 1].contiguous() for g in gts)
+        out = {'flow_fw': torch.empty(1, h, w, 2, device=device), 'flow_bw': torch.empty(1, h, w, 2, device=device)}
+        for k in ('flow_fw_u8', 'flow_bw_u8') + tuple(f'gt_{d}_u8' for d, g in zip(('fw', 'bw'), gt) if g is not None):
+            out[k] = torch.empty(1, h, w, 3, dtype=torch.uint8, device=device)
+        sums = torch.empty(1, 2, 3, dtype=torch.float64, device=device) if have_gt else None
+        counts = torch.empty(1, 2, 3, dtype=torch.int64, device=device) if have_gt else None
+        # prediction and ground truth share the ground truth's radius unless one is given
+        rad = torch.empty(1, 2, 2, device=device)
+        _lib.flow_maps(1, h, w, xyz=(res['xyz_fw'].view(1, h * w, 3), res['xyz_bw'].view(1, h * w, 3)), K4=K4, Ps=Ps,
+                       ts=ts[:1].to(torch.int32), max_t=n - 1, flow=(out['flow_fw'], out['flow_bw']), gt=gt,
+                       mask=None if masks is None or not have_gt else _mask_u8(masks[i:i + 1]), epe_sums=sums,
+                       epe_counts=counts, maxrad=rad, scale=scale, share_gt_scale=have_gt and scale is None,
+                       image=(out['flow_fw_u8'], out['flow_bw_u8']), gt_image=(out.get('gt_fw_u8'), out.get('gt_bw_u8')),
+                       scratch=scratch)
+        if have_gt:
+            scores.add(sums[0], counts[0])
+        else:
+            nan = torch.full((2, 3), float('nan'), dtype=torch.float64, device=device)
+            scores.add(nan, torch.zeros(2, 3, dtype=torch.int64, device=device))
+        maps = {k: v[0] for k, v in out.items()}
+        if pools is None:
+            yield names[i], maps
+            continue
+        if device not in _COPY_STREAM:
+            _COPY_STREAM[device] = torch.cuda.Stream(device=device)
+        copy_stream = _COPY_STREAM[device]
+        slots = [p.next_slot() for p in pools]
+        host = HostFrame()
+        done = torch.cuda.Event()
+        done.record()                                         # this frame's launches, on the render stream
+        with torch.cuda.stream(copy_stream):
+            copy_stream.wait_event(done)
+            for key, t in maps.items():
+                which = 1 if t.dtype == torch.uint8 else 0
+                host[key] = pools[which].buffer(slots[which], key, tuple(t.shape))
+                host[key].copy_(t, non_blocking=True)
+                t.record_stream(copy_stream)
+            host.event = torch.cuda.Event()
+            host.event.record(copy_stream)
+        for p, s in zip(pools, slots):
+            p._last[s] = host
+        if pending is not None:
+            yield land(pending)                               # frame i - 1: its copy ran beside this frame's render
+        pending = (names[i], host)
+    if pending is not None:
+        yield land(pending)
+
+
+def _mask_u8(mask):
+    return (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()

@@ -11,6 +11,9 @@ upload + one launch) and the launch alone; it reads 3 + 4 + 1 + 16 B and writes 
 metrics.finish_frames on 1 and 100 frames with every input and output (csrc/metrics.hip::frame_image_kernel + frame_depth_kernel):
 the whole call (output allocation + two launches) and nsff_frame_finish alone on preallocated outputs.  The image pass reads
 12 + 12 + 1 + 4 B and writes 12 + 3 B per pixel, the depth pass reads 4 B and writes 1 + 3 B: 52 B per pixel.
+flow_frames' kernel work on 1 and 100 frames, both directions with ground truth and mask (csrc/flow.hip::flow_map_kernel +
+flow_colour_kernel): nsff_flow_maps alone on preallocated outputs, its two launches separately, and the projection alone.  Per pixel and direction the
+map pass reads 12 + 8 B and writes 8 B, the colour pass reads 8 + 8 B and writes 3 + 3 B, plus the 1-B mask: 101 B per pixel.
 """
 import argparse
 import json
@@ -79,15 +82,64 @@ def bench_finish_frames(dev, g, W, H, reps, F):
             f"frame_finish_F{F}_bound_us": F * H * W * FINISH_BYTES_PER_PIXEL / HBM_PEAK * 1e6}
 
 
+FLOW_MAP_BYTES_PER_PIXEL = 2 * (12 + 8 + 8) + 1
+FLOW_COLOUR_BYTES_PER_PIXEL = 2 * (8 + 8 + 3 + 3)
+
+
+def bench_flow_frames(dev, g, W, H, reps, F):
+    K4 = [400.0, 400.0, W / 2, H / 2]
+    n_poses = F + 2
+    Ps = torch.zeros(n_poses, 3, 4, device=dev)
+    Ps[:, 0, 0], Ps[:, 1, 1], Ps[:, 2, 2] = K4[0], -K4[1], -1.0     # K diag(1, -1, -1) [I | t]
+    Ps[:, 0, 2], Ps[:, 1, 2] = -K4[2], -K4[3]
+    Ps[:, :, 3] = torch.rand(n_poses, 3, device=dev, generator=g) * 0.2 - 0.1
+    ts = torch.arange(1, F + 1, device=dev, dtype=torch.int32)
+    xyz = tuple(torch.cat([torch.rand(F, H * W, 2, device=dev, generator=g) * 2 - 1,
+                           torch.rand(F, H * W, 1, device=dev, generator=g) * 1.9 - 1], -1).contiguous() for _ in range(2))
+    gt = tuple(3 * torch.randn(F, H, W, 2, device=dev, generator=g) for _ in range(2))
+    mask = (torch.rand(F, H, W, device=dev, generator=g) < 0.3).to(torch.uint8)
+    u8 = lambda: torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    maps = dict(flow=(torch.empty(F, H, W, 2, device=dev), torch.empty(F, H, W, 2, device=dev)),
+                epe_sums=torch.empty(F, 2, 3, dtype=torch.float64, device=dev),
+                epe_counts=torch.empty(F, 2, 3, dtype=torch.int64, device=dev), maxrad=torch.empty(F, 2, 2, device=dev))
+    images = dict(image=(u8(), u8()), gt_image=(u8(), u8()))
+    scratch = torch.zeros(_lib.flow_maps_scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    both = lambda: _lib.flow_maps(F, H, W, xyz=xyz, K4=K4, Ps=Ps, ts=ts, max_t=n_poses - 1, gt=gt, mask=mask, share_gt_scale=True,
+                                  scratch=scratch, **maps, **images)
+    first = lambda: _lib.flow_maps(F, H, W, xyz=xyz, K4=K4, Ps=Ps, ts=ts, max_t=n_poses - 1, gt=gt, mask=mask, scratch=scratch, **maps)
+    project = lambda: _lib.flow_maps(F, H, W, xyz=xyz, K4=K4, Ps=Ps, ts=ts, max_t=n_poses - 1, flow=maps["flow"])
+    second = lambda: _lib.flow_maps(F, H, W, flow=maps["flow"], gt=gt, scale=maps["maxrad"], share_gt_scale=True, **images)
+    px = F * H * W
+    return {f"flow_frames_F{F}_us": time_us(both, reps),
+            f"flow_frames_F{F}_bound_us": px * (FLOW_MAP_BYTES_PER_PIXEL + FLOW_COLOUR_BYTES_PER_PIXEL) / HBM_PEAK * 1e6,
+            f"flow_map_F{F}_us": time_us(first, reps),
+            f"flow_map_F{F}_bound_us": px * FLOW_MAP_BYTES_PER_PIXEL / HBM_PEAK * 1e6,
+            f"flow_project_F{F}_us": time_us(project, reps),               # the map pass without ground truth or reduction
+            f"flow_project_F{F}_bound_us": px * 2 * (12 + 8) / HBM_PEAK * 1e6,
+            f"flow_colour_F{F}_us": time_us(second, reps),
+            f"flow_colour_F{F}_bound_us": px * FLOW_COLOUR_BYTES_PER_PIXEL / HBM_PEAK * 1e6}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow (default: everything)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
     px = W * H
     g = torch.Generator(dev).manual_seed(0)
     out = {"frame": [W, H], "hbm_peak_TBps": HBM_PEAK / 1e12}
+    only = [c for c in args.only.split(",") if c]
+    if only:
+        for F in (1, 100):
+            if "finish" in only:
+                out.update(bench_finish_frames(dev, g, W, H, args.reps, F))
+            if "flow" in only:
+                out.update(bench_flow_frames(dev, g, W, H, args.reps, F))
+            torch.cuda.empty_cache()
+        print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
+        return
     gt = torch.rand(H, W, 3, device=dev, generator=g)
     pred = (gt + 0.05 * torch.randn(H, W, 3, device=dev, generator=g)).clamp(0, 1)
     out["ssim_512x288_us"] = time_us(lambda: metrics.ssim(gt, pred), args.reps)
@@ -106,6 +158,7 @@ def main():
     out.update(bench_build_records(dev, g, W, H, args.reps))
     for F in (1, 100):
         out.update(bench_finish_frames(dev, g, W, H, args.reps, F))
+        out.update(bench_flow_frames(dev, g, W, H, args.reps, F))
         torch.cuda.empty_cache()
     print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
 
