@@ -786,6 +786,50 @@ typedef struct NsffFrameFinishArgs {
 int64_t nsff_frame_finish_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
 int nsff_frame_finish(const NsffFrameFinishArgs* args, void* stream);
 
+/* The image panels of the trainer's validation step (train.py:209-235, 254-257 over utils/visualization.py:6-44 and
+ * torchvision's make_grid) for n_frames frames of H x W pixels, as 8-bit images.  Only pred is required; every other pointer may be
+ * NULL and every output is written only when given.  Inputs, fp32, (F, H*W[, 3]) contiguous, channels last: gt; pred, the raw
+ * rgb_fine; depth; transient_alpha, static_rgb (the raw _static_rgb_fine) and static_depth -- all three or none; mask (0 = static,
+ * 1 = dynamic, as the validation batch carries it); disp; ssim_loss (F, H*W, 3), the `map` of nsff_ssim for (gt, clip(pred)).
+ * lut_depth / lut_mask (256, 3) uint8 stand for cv2.applyColorMap(., COLORMAP_JET) / (., COLORMAP_BONE) and are used as they are
+ * (the reference hands cv2's BGR bytes to PIL unchanged); a NULL table writes the index into all three channels.
+ * Two error maps are formed per pixel, every step one fp32 operation (divide and square root correctly rounded):
+ *   rmse = sqrt(((d0^2 + d1^2) + d2^2) / 3), d = gt - clip(pred, 0, 1)          (train.py:215)
+ *   ssim = (((1 - l0) + (1 - l1)) + (1 - l2)) / 3, l = ssim_loss                (train.py:218)
+ * Launch 1 writes
+ *   ranges  (F, 5, 2) fp32   min and max of nan_to_num of [depth, static_depth, -disp, -rmse (needs gt), -ssim (needs ssim_loss)];
+ *                            the rows of missing fields are left untouched.  Combined from per-workgroup partials in an order
+ *                            that depends on H * W only: the same bits for a frame alone or in a batch.
+ * Launch 2 (only with one of the outputs below) recomputes the maps and writes, with index(x) = the 8-bit index of
+ * visualize_depth, 255 * ((x - min) / (max - min + 1e-8f)) truncated, on the frame's own range of that field:
+ *   rmse_u8, ssim_u8  (F, H*W) uint8            index(-rmse), index(-ssim);
+ *   rmse_blend_u8, ssim_blend_u8  (F, H*W, 3)   blend_images(clip(pred), visualize_depth(-map), 0.5): with a = the 8-bit clipped
+ *                            prediction and b = lut_depth[index] per channel, min(255, ((a + b) >> 1) + 2 + ((a + b) & 1)), which
+ *                            is cv2.addWeighted(a, .5, b, .5, 2.2) = saturate(round(a / 2 + b / 2 + 2.2)) for every byte pair;
+ *   grid_u8  (F, GH, GW, 3) uint8               make_grid(tiles, nrow=3) with padding 2 and pad value 0: tile k at row
+ *                            (k / 3)(H + 2) + 2, column (k % 3)(W + 2) + 2; GW = 3 (W + 2) + 2, GH = ymaps (H + 2) + 2, ymaps =
+ *                            ceil(tiles / 3).  Tiles in order (train.py:225-231): gt, clip(pred), depth colour [, transient_alpha
+ *                            through visualize_mask, clip(static_rgb), static-depth colour] [, 1 - mask through visualize_mask]
+ *                            [, -disp colour]: 3 to 8 of them (needs gt and depth).  Padding and unfilled cells are written as 0.
+ *                            Float tiles are 255 * x truncated, colour tiles lut_depth[index(x)], mask tiles lut_mask[255 * x
+ *                            truncated].  Every truncation CLAMPS to 0..255 first (a NaN gives 0) -- numpy's astype(uint8) of a
+ *                            value outside that range (a ground truth above 1, an alpha below 0) is platform-defined.
+ * No synchronisation, no allocation: capturable.  `scratch`: nsff_val_panels_scratch_bytes() bytes, 16-byte aligned, ZERO before
+ * its first use (every call returns its counter words to zero; one call at a time per scratch buffer).  n_frames <= 65535 and
+ * 1 <= H * W < 2^31; a missing pred or ranges, an output without its input, a transient set given in part or no field at all is
+ * NSFF_ERR_INVALID, before any launch.  fp32 arrays 16-byte and the (F, H*W[, 3]) uint8 outputs 4-byte aligned take the wide
+ * path, less aligned ones go element by element; the grid's 3-byte pixels are packed into dword stores by address. */
+typedef struct NsffValPanelsArgs {
+    int32_t n_frames, H, W, pad_;
+    const float* gt;  const float* pred;  const float* depth;  const float* transient_alpha;  const float* static_rgb;
+    const float* static_depth;  const float* mask;  const float* disp;  const float* ssim_loss;
+    const uint8_t* lut_depth;  const uint8_t* lut_mask;
+    float* ranges;  uint8_t* grid_u8;  uint8_t* rmse_u8;  uint8_t* ssim_u8;  uint8_t* rmse_blend_u8;  uint8_t* ssim_blend_u8;
+    void* scratch;  int64_t scratch_bytes;
+} NsffValPanelsArgs;
+int64_t nsff_val_panels_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int nsff_val_panels(const NsffValPanelsArgs* args, void* stream);
+
 /* ---- induced optical flow of rendered frames: maps, end-point error, colour images (csrc/flow.hip).
  * What the reference's test.ipynb does on the host with the test-time outputs xyz_fw / xyz_bw (rendering.py:280-287), for
  * n_frames frames of H x W pixels and both directions (index 0 forward, 1 backward) in one call.  Three stages, selected by the

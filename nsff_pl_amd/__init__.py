@@ -16,8 +16,11 @@ from .frames import build_records, projection_matrices
 from .sampling import RayBank
 from . import flow
 from .flow import induced_flow, flow_to_image, flow_epe, epe_from_sums
+from . import panels
+from .panels import validation_panels, error_blend
 
 __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "set_precision", "get_precision",
            "set_range_check", "get_range_check", "range_flags", "RangeFlags",
            "build_records", "projection_matrices", "RayBank",
-           "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums"]
+           "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
+           "panels", "validation_panels", "error_blend"]

@@ -176,7 +176,18 @@ class FrameFinishArgs(C.Structure):
                 + [(n, _fp) for n in _FINISH_PTRS] + [("scratch", _fp), ("scratch_bytes", C.c_int64)])
 
 
-FLOW_UNKNOWN = 1e10            # NSFF_FLOW_UNKNOWN: both components of an induced-flow pixel without a valid projection
+_PANEL_IN = ["gt", "pred", "depth", "transient_alpha", "static_rgb", "static_depth", "mask", "disp", "ssim_loss"]
+_PANEL_LUT = ["lut_depth", "lut_mask"]
+_PANEL_OUT = ["ranges", "grid_u8", "rmse_u8", "ssim_u8", "rmse_blend_u8", "ssim_blend_u8"]
+PANEL_FIELDS = ("depth", "static_depth", "neg_disp", "neg_rmse", "neg_ssim")          # the rows of `ranges`
+
+
+class ValPanelsArgs(C.Structure):
+    _fields_ = ([("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pad_", C.c_int32)]
+                + [(n, _fp) for n in _PANEL_IN + _PANEL_LUT + _PANEL_OUT] + [("scratch", _fp), ("scratch_bytes", C.c_int64)])
+
+
+FLOW_UNKNOWN = 1e10           # NSFF_FLOW_UNKNOWN: both components of an induced-flow pixel without a valid projection
 
 
 class FlowMapsArgs(C.Structure):
@@ -284,6 +295,8 @@ _SIGNATURES = {
     "nsff_ssim": (C.c_int, [C.POINTER(SsimArgs), _fp]),
     "nsff_frame_finish_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_frame_finish": (C.c_int, [C.POINTER(FrameFinishArgs), _fp]),
+    "nsff_val_panels_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_val_panels": (C.c_int, [C.POINTER(ValPanelsArgs), _fp]),
     "nsff_flow_maps_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_flow_maps": (C.c_int, [C.POINTER(FlowMapsArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
@@ -1107,6 +1120,44 @@ def frame_finish(rgb, gt=None, valid=None, depth=None, lut=None, rgb_clipped=Non
         setattr(a, name, _dptr(t, dtypes.get(name, torch.uint8), f"frame_finish: {name}"))
     with torch.cuda.device(rgb.device):
         _check(load().nsff_frame_finish(C.byref(a), _stream()), "nsff_frame_finish")
+
+
+def val_panels_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_val_panels_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def panel_grid_shape(H, W, n_tiles):
+    """(GH, GW) of make_grid(n_tiles images of H x W, nrow=3, padding=2)."""
+    return -(-int(n_tiles) // 3) * (int(H) + 2) + 2, 3 * (int(W) + 2) + 2
+
+
+def val_panels(F, H, W, pred, gt=None, depth=None, transient_alpha=None, static_rgb=None, static_depth=None, mask=None, disp=None,
+               ssim_loss=None, lut_depth=None, lut_mask=None, ranges=None, grid_u8=None, rmse_u8=None, ssim_u8=None,
+               rmse_blend_u8=None, ssim_blend_u8=None, scratch=None):
+    """nsff_val_panels on F frames of H x W pixels: fp32 inputs of F*H*W[*3] elements, lut_* (256, 3) uint8 -> whichever of ranges
+    (F, 5, 2) fp32, grid_u8 (F, GH, GW, 3), rmse_u8 / ssim_u8 (F, H, W) and rmse_blend_u8 / ssim_blend_u8 (F, H, W, 3) uint8 are given.
+    scratch: uint8 tensor of val_panels_scratch_bytes() bytes, zero before its first use (a fresh zeroed one when None)."""
+    F, H, W = int(F), int(H), int(W)
+    require_gpu_tensor(pred, "val_panels: pred")
+    dev, n = pred.device, F * H * W
+    if scratch is None:
+        scratch = torch.zeros(max(val_panels_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    given = dict(gt=gt, pred=pred, depth=depth, transient_alpha=transient_alpha, static_rgb=static_rgb, static_depth=static_depth,
+                 mask=mask, disp=disp, ssim_loss=ssim_loss, lut_depth=lut_depth, lut_mask=lut_mask, ranges=ranges, grid_u8=grid_u8,
+                 rmse_u8=rmse_u8, ssim_u8=ssim_u8, rmse_blend_u8=rmse_blend_u8, ssim_blend_u8=ssim_blend_u8)
+    n_tiles = 3 + (3 if transient_alpha is not None else 0) + (mask is not None) + (disp is not None)
+    GH, GW = panel_grid_shape(H, W, n_tiles)
+    sizes = dict(gt=n * 3, pred=n * 3, depth=n, transient_alpha=n, static_rgb=n * 3, static_depth=n, mask=n, disp=n, ssim_loss=n * 3,
+                 lut_depth=768, lut_mask=768, ranges=F * 10, grid_u8=F * GH * GW * 3, rmse_u8=n, ssim_u8=n, rmse_blend_u8=n * 3,
+                 ssim_blend_u8=n * 3)
+    a = ValPanelsArgs(n_frames=F, H=H, W=W, scratch=_dptr(scratch, torch.uint8, "val_panels: scratch"), scratch_bytes=scratch.numel())
+    for name, t in given.items():
+        if t is not None and (t.numel() != sizes[name] or t.device != dev):
+            raise RuntimeError(f"val_panels: {name} has {t.numel()} elements on {t.device}, expected {sizes[name]} on {dev}")
+        fp32 = name in _PANEL_IN or name == "ranges"
+        setattr(a, name, _dptr(t, torch.float32 if fp32 else torch.uint8, f"val_panels: {name}"))
+    with torch.cuda.device(dev):
+        _check(load().nsff_val_panels(C.byref(a), _stream()), "nsff_val_panels")
 
 
 def flow_maps_scratch_bytes(n_frames, H, W):

@@ -536,10 +536,13 @@ __device__ __forceinline__ int block_sum_int(int v, int* sRed) {           // 25
     return sRed[0] + sRed[1] + sRed[2] + sRed[3];
 }
 
-// zero both families' histograms (a kernel, not hipMemsetAsync: with the memset a replayed capture of the call saw empty histograms)
-__global__ __launch_bounds__(256) void sel_clear_kernel(const SelWork w) {
+// zero both families' histograms and the stats buffer (a kernel, not hipMemsetAsync: with the memset a replayed capture of the
+// call saw empty histograms, and a replayed 96-byte memset of `stats` was seen to leave non-zero words in stats[18..23], i.e.
+// under the ST_DOCCS atomics, which halved cyc_l)
+__global__ __launch_bounds__(256) void sel_clear_kernel(const SelWork w, float* __restrict__ stats) {
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
     if (i < 2 * SEL_HIST_WORDS / 4) reinterpret_cast<uint4*>(w.hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (i < (unsigned)ST_SIZE) stats[i] = 0.f;
 }
 
 // pass `p` of the digit histograms; grid (nb, vectors)
@@ -704,9 +707,7 @@ int nsff_nerfw_loss_ex(const NsffLossArgs* args, int mode, void* work, size_t wo
     w.count = (unsigned*)((char*)work + sel_hist_bytes());
     w.partial = (double*)((char*)work + sel_hist_bytes() + cnt);
     const bool ranked = a.topk < 1.0;             // plain means need the populations (pass 0) only
-    const hipError_t e = hipMemsetAsync(a.stats, 0, ST_SIZE * sizeof(float), st);
-    if (e != hipSuccess) return nsff_hip_fail(e);
-    hipLaunchKernelGGL(sel_clear_kernel, dim3((unsigned)((2 * SEL_HIST_WORDS / 4 + 255) / 256)), dim3(256), 0, st, w);
+    hipLaunchKernelGGL(sel_clear_kernel, dim3((unsigned)((2 * SEL_HIST_WORDS / 4 + 255) / 256)), dim3(256), 0, st, w, a.stats);
     const long long total = a.n_rays * a.n_samples;
     const dim3 gm((unsigned)w.nb, 3), gs((unsigned)w.nb, N_TERMS);
     hipLaunchKernelGGL(loss_sums_kernel, dim3((unsigned)std::min<long long>((total + 2047) / 2048, 256)), dim3(256), 0, st, a);

@@ -124,6 +124,11 @@ class RayBank:
         return {"rays": r[:, :6].contiguous(), "ts": r[:, 9].long(), "rgbs": r[:, 6:9].contiguous(),
                 "disp": r[:, 10].contiguous(), "mask": r[:, 11].contiguous()}
 
+    def frame_images(self, t):
+        """``(ground truth, tmp_rgb)`` of frame t as (H, W, 3) views: the pair train.py:250-251 compares."""
+        W, H = self.img_wh
+        return self.rgb[int(t)].view(H, W, 3), self.tmp_rgb[int(t)].view(H, W, 3)
+
     @torch.no_grad()
     def record(self, batch, rgb_fine):
         """train.py:184-185: tmp_rgb[ts, rand_idx] = rgb_fine (capturable)."""

@@ -12,7 +12,8 @@ Validation reports the reference's ``val_psnr`` and, given the hparam ``img_wh``
 ``val_ssim_mask`` for a batch with a dynamic ``mask``; train.py:200-243) with the SSIM kernel of :mod:`nsff_pl_amd.metrics`.
 ``--hard_sampling`` (train.py:140-143, 184-185, 246-253) is a :class:`nsff_pl_amd.sampling.RayBank` passed as ``ray_bank``:
 the step records ``rgb_fine`` into the bank's ``tmp_rgb`` and validation re-weights the bank's pixels.
-Logging, checkpoint callbacks and validation images of the reference are control plane and out of scope.
+``validation_step(batch, panels=...)`` also composes the reference's validation image grids on the GPU (:mod:`nsff_pl_amd.panels`).
+Logging and checkpoint callbacks of the reference are control plane and out of scope.
 """
 from collections import defaultdict
 
@@ -23,6 +24,7 @@ import torch.distributed as dist
 
 from . import field_grad
 from . import metrics
+from . import panels as panel_images
 from . import range_check
 from .autograd import grad_parameters
 from .losses import NeRFWLoss
@@ -266,13 +268,25 @@ class NSFFTrainer:
     def _hard_sampling(self):
         return self.ray_bank is not None and self.ray_bank.hard_sampling
 
-    # train.py:200-253 (the metric part and the hard-sampling update; image grids of the reference are logging)
+    # train.py:200-257 (the metrics, the hard-sampling update and, on request, the image grids the reference logs)
     @torch.no_grad()
-    def validation_step(self, batch):
-        """batch: {'rays': (H*W,6), 'rgbs': (H*W,3) [, 'ts'] [, 'mask': (H*W)]} of one full frame -> {'val_psnr'}; with the
-        hparam img_wh also 'val_ssim' (the reference's SSIM of the clipped prediction, train.py:209-219), and with a 'mask'
-        that has static pixels (mask == 0) and output_transient on, 'val_psnr_mask' / 'val_ssim_mask' over those pixels
-        (train.py:240-243).  A hard-sampling ray bank is re-weighted afterwards (train.py:246-253)."""
+    def validation_step(self, batch, panels=None):
+        """batch: {'rays': (H*W,6), 'rgbs': (H*W,3) [, 'ts'] [, 'mask': (H*W)] [, 'disp': (H*W)]} of one full frame ->
+        {'val_psnr'}; with the hparam img_wh also 'val_ssim' (the reference's SSIM of the clipped prediction, train.py:209-219),
+        and with a 'mask' that has static pixels (mask == 0) and output_transient on, 'val_psnr_mask' / 'val_ssim_mask' over
+        those pixels (train.py:240-243).  A hard-sampling ray bank is re-weighted afterwards (train.py:246-253).
+
+        panels: None (the default) returns the metrics alone.  ``dict(lut_depth=..., lut_mask=...)`` -- the (256, 3) uint8
+        tables standing for cv2's JET / BONE colour maps -- or ``True`` (index-grey panels) adds ``log['panels']``: the uint8
+        GPU images of :func:`nsff_pl_amd.panels.validation_panels` under the reference's tags ('reconstruction/decomposition',
+        'error_map/rmse', 'error_map/ssim'; train.py:215-235), and with a hard-sampling bank 'misc/moving_ssim', the SSIM blend
+        of the bank's frame N_frames // 2 after the re-weighting (train.py:254-257).  Deviation: the reference quantises the
+        unclipped ``tmp_rgb`` there (numpy's cast of a value outside 0..255 is platform-defined); the prediction is clipped to
+        [0, 1] first here, as for every other panel.  Needs img_wh; nothing is read back to the host."""
+        if panels is False:
+            panels = None
+        if panels is not None and self.hp["img_wh"] is None:
+            raise ValueError("validation_step: panels need the hparam img_wh")
         kwargs = dict(output_transient=self.output_transient, output_transient_flow=[])
         results = self.forward(batch["rays"], batch.get("ts"), test_time=True, **kwargs)
         rgb, rgbs = results["rgb_fine"], batch["rgbs"]
@@ -291,8 +305,17 @@ class NSFFTrainer:
             if static is not None:
                 log["val_psnr_mask"] = metrics.psnr(rgb, rgbs, static.reshape(-1))
                 log["val_ssim_mask"] = frame_mask[0]
+        if panels is not None:
+            luts = {} if panels is True else dict(panels)
+            log["panels"] = panel_images.validation_panels(results, batch, self.hp["img_wh"], lut_depth=luts.get("lut_depth"),
+                                                           lut_mask=luts.get("lut_mask"), output_transient=self.output_transient)
         if self._hard_sampling():
             self.update_hard_sampling()
+            if panels is not None:
+                # (the re-weighting keeps only the channel mean of every frame's loss map: the middle frame's map is one more launch)
+                gt_mid, tmp_mid = self.ray_bank.frame_images(self.ray_bank.n_frames // 2)
+                log["panels"]["misc/moving_ssim"] = panel_images.error_blend(gt_mid, tmp_mid, "ssim", lut=luts.get("lut_depth"),
+                                                                             clip_ssim=False)
         return log
 
     def update_hard_sampling(self):

@@ -14,6 +14,10 @@ the whole call (output allocation + two launches) and nsff_frame_finish alone on
 flow_frames' kernel work on 1 and 100 frames, both directions with ground truth and mask (csrc/flow.hip::flow_map_kernel +
 flow_colour_kernel): nsff_flow_maps alone on preallocated outputs, its two launches separately, and the projection alone.  Per pixel and direction the
 map pass reads 12 + 8 B and writes 8 B, the colour pass reads 8 + 8 B and writes 3 + 3 B, plus the 1-B mask: 101 B per pixel.
+The validation panels (--only panel) on 1 and 30 frames with all eight tiles (csrc/metrics.hip::panel_range_kernel +
+panel_compose_kernel): nsff_val_panels alone on preallocated outputs and its range launch alone.  The range pass reads gt, pred, depth,
+static depth, disp and the SSIM loss map (48 B per pixel); the compose pass reads those again plus alpha, static rgb and mask
+(68 B) and writes the two index images, the two blends and nine grid cells (1 + 1 + 3 + 3 + 27 B): 151 B per pixel.
 """
 import argparse
 import json
@@ -120,10 +124,36 @@ def bench_flow_frames(dev, g, W, H, reps, F):
             f"flow_colour_F{F}_bound_us": px * FLOW_COLOUR_BYTES_PER_PIXEL / HBM_PEAK * 1e6}
 
 
+PANEL_RANGE_BYTES_PER_PIXEL = 12 + 12 + 4 + 4 + 4 + 12
+PANEL_COMPOSE_BYTES_PER_PIXEL = PANEL_RANGE_BYTES_PER_PIXEL + (4 + 12 + 4) + (1 + 1 + 3 + 3 + 9 * 3)
+
+
+def bench_panels(dev, g, W, H, reps, F):
+    rand = lambda *shape: torch.rand(*shape, device=dev, generator=g)
+    gt = rand(F, H * W, 3)
+    ins = dict(gt=gt, depth=rand(F, H * W) * 4, transient_alpha=rand(F, H * W), static_rgb=rand(F, H * W, 3) * 1.2 - 0.1,
+               static_depth=rand(F, H * W) * 4, mask=(rand(F, H * W) < 0.3).float(), disp=rand(F, H * W) * 2, ssim_loss=rand(F, H * W, 3) * 0.2,
+               lut_depth=torch.randint(0, 256, (256, 3), device=dev, generator=g, dtype=torch.uint8),
+               lut_mask=torch.randint(0, 256, (256, 3), device=dev, generator=g, dtype=torch.uint8))
+    pred = gt + 0.1 * torch.randn(F, H * W, 3, device=dev, generator=g)
+    GH, GW = _lib.panel_grid_shape(H, W, 8)
+    u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)
+    ranges = torch.empty(F, 5, 2, device=dev)
+    outs = dict(grid_u8=u8(F, GH, GW, 3), rmse_u8=u8(F, H * W), ssim_u8=u8(F, H * W), rmse_blend_u8=u8(F, H * W, 3), ssim_blend_u8=u8(F, H * W, 3))
+    scratch = torch.zeros(_lib.val_panels_scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    both = lambda: _lib.val_panels(F, H, W, pred, ranges=ranges, scratch=scratch, **ins, **outs)
+    first = lambda: _lib.val_panels(F, H, W, pred, ranges=ranges, scratch=scratch, **ins)
+    px = F * H * W
+    return {f"val_panels_F{F}_us": time_us(both, reps),
+            f"val_panels_F{F}_bound_us": px * (PANEL_RANGE_BYTES_PER_PIXEL + PANEL_COMPOSE_BYTES_PER_PIXEL) / HBM_PEAK * 1e6,
+            f"panel_range_F{F}_us": time_us(first, reps),
+            f"panel_range_F{F}_bound_us": px * PANEL_RANGE_BYTES_PER_PIXEL / HBM_PEAK * 1e6}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow (default: everything)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel (default: everything)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -138,6 +168,9 @@ def main():
             if "flow" in only:
                 out.update(bench_flow_frames(dev, g, W, H, args.reps, F))
             torch.cuda.empty_cache()
+        if "panel" in only:
+            for F in (1, 30):
+                out.update(bench_panels(dev, g, W, H, args.reps, F))
         print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
         return
     gt = torch.rand(H, W, 3, device=dev, generator=g)
@@ -160,6 +193,8 @@ def main():
         out.update(bench_finish_frames(dev, g, W, H, args.reps, F))
         out.update(bench_flow_frames(dev, g, W, H, args.reps, F))
         torch.cuda.empty_cache()
+    for F in (1, 30):
+        out.update(bench_panels(dev, g, W, H, args.reps, F))
     print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
 
 
