@@ -22,21 +22,20 @@
 // wave and a workgroup add depends on H * W alone: a frame's sums and radii are the same bits at any position of any batch.  The
 // 12-byte points would give each lane a 12-byte stride; instead the workgroup's 12 KiB of each direction are copied to LDS as one
 // contiguous run (16-byte loads where the run starts 16-byte aligned, dwords otherwise) and read from there at a 3-dword lane
-// stride, which is free of bank conflicts (3 is odd).  Per-workgroup partials go to scratch as agent-scope atomic stores (no
-// release fence: DESIGN.md section 11 on what a fence per workgroup costs) and the frame's last-arriving workgroup adds them in
-// block order, as frame_image_kernel does.
+// stride, which is free of bank conflicts (3 is odd).  Per-workgroup partials go to scratch and the frame's last-arriving workgroup
+// adds them in block order: the ticketed reduction of nsff_frame_ops.h, which frame_image_kernel (frames.hip) uses too.
 #include <hip/hip_runtime.h>
-#include <cfloat>
 #include <cstdint>
 #include <cmath>
 
 #include "../../include/nsff_render.h"
 #include "nsff_common.h"
+#include "nsff_frame_ops.h"
 
 namespace {
 
 constexpr int FLOW_THREADS = 256, FLOW_PX = 4, FLOW_BLOCK_PX = FLOW_THREADS * FLOW_PX;
-constexpr int FLOW_PARTIAL_WORDS = 11;                            // 6 fp64 sums, 6 uint32 counts, 4 fp32 radii: 88 bytes
+constexpr int FLOW_WORDS = 11;                                    // one workgroup's share of a frame: 6 fp64 sums, 6 uint32 counts, 4 fp32 radii
 constexpr float FLOW_THRESH = 1e7f;                               // flowlib's UNKNOWN_FLOW_THRESH
 constexpr int WHEEL = 55;                                         // RY 15 + YG 6 + GC 4 + CB 11 + BM 13 + MR 6
 
@@ -44,7 +43,7 @@ constexpr int WHEEL = 55;                                         // RY 15 + YG 
 __device__ __forceinline__ bool flow_known(float u, float v) { return fabsf(u) <= FLOW_THRESH && fabsf(v) <= FLOW_THRESH; }
 
 __global__ __launch_bounds__(FLOW_THREADS) void flow_map_kernel(NsffFlowMapsArgs a, int reduce, unsigned* __restrict__ counters,
-                                                                unsigned long long* __restrict__ partials) {
+                                                                frame_word* __restrict__ partials) {
     __shared__ float s_xyz[2][FLOW_BLOCK_PX * 3];
     __shared__ double s_sum[FLOW_THREADS / 64][6];
     __shared__ uint32_t s_cnt[FLOW_THREADS / 64][6];
@@ -143,16 +142,12 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_map_kernel(NsffFlowMapsArgs
     }
     if (!reduce) return;
 
-    // workgroup reduction in a fixed order: butterfly within each wave, then the four waves in order
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int d = 0; d < 2; ++d) {
 #pragma unroll
-        for (int d = 0; d < 2; ++d) {
+        for (int k = 0; k < 3; ++k) { sum[d][k] = wave_sum(sum[d][k]); cnt[d][k] = wave_sum(cnt[d][k]); }
 #pragma unroll
-            for (int k = 0; k < 3; ++k) { sum[d][k] += __shfl_xor(sum[d][k], o); cnt[d][k] += __shfl_xor(cnt[d][k], o); }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) rad[d][k] = fmaxf(rad[d][k], __shfl_xor(rad[d][k], o));
-        }
+        for (int k = 0; k < 2; ++k) rad[d][k] = wave_max(rad[d][k]);
     }
     if (lane == 0) {
 #pragma unroll
@@ -165,62 +160,37 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_map_kernel(NsffFlowMapsArgs
     }
     __syncthreads();
     if (wave != 0) return;
-    const int64_t n_blocks = gridDim.x;
-    unsigned long long* fp = partials + f * n_blocks * FLOW_PARTIAL_WORDS;
-    unsigned ticket = 0;
-    if (lane == 0) {
-        unsigned long long w[FLOW_PARTIAL_WORDS];
-        uint32_t c[6];
-        float r[4];
-        for (int i = 0; i < 6; ++i) {
-            w[i] = (unsigned long long)__double_as_longlong(((s_sum[0][i] + s_sum[1][i]) + s_sum[2][i]) + s_sum[3][i]);
-            c[i] = ((s_cnt[0][i] + s_cnt[1][i]) + s_cnt[2][i]) + s_cnt[3][i];
-        }
-        for (int i = 0; i < 4; ++i) r[i] = fmaxf(fmaxf(s_rad[0][i], s_rad[1][i]), fmaxf(s_rad[2][i], s_rad[3][i]));
-        for (int i = 0; i < 3; ++i) w[6 + i] = (unsigned long long)c[2 * i] | ((unsigned long long)c[2 * i + 1] << 32);
-        for (int i = 0; i < 2; ++i) w[9 + i] = (unsigned long long)__float_as_uint(r[2 * i]) | ((unsigned long long)__float_as_uint(r[2 * i + 1]) << 32);
-        // publish the partial as agent-scope atomic stores (write-through: no release fence), then take a ticket
-        unsigned long long* slot = fp + (int64_t)blockIdx.x * FLOW_PARTIAL_WORDS;
-        for (int i = 0; i < FLOW_PARTIAL_WORDS; ++i) __hip_atomic_store(slot + i, w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ticket = __hip_atomic_fetch_add(counters + f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    ticket = __shfl(ticket, 0);
-    if (ticket != (unsigned)(n_blocks - 1)) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned n_blocks = gridDim.x;
+    frame_word* fp = partials + f * n_blocks * FLOW_WORDS;
+    frame_word mine[FLOW_WORDS];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) mine[i] = pack_double(sum4(s_sum, i));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) mine[6 + i] = pack2(sum4(s_cnt, 2 * i), sum4(s_cnt, 2 * i + 1));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) mine[9 + i] = pack2(max4(s_rad, 2 * i), max4(s_rad, 2 * i + 1));
+    if (!frame_publish(fp, counters + f, blockIdx.x, n_blocks, lane, mine)) return;
     double tot[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     long long n[6] = {0, 0, 0, 0, 0, 0};
     float r[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t t = lane; t < n_blocks; t += 64) {               // lane l adds blocks l, l + 64, ... in order
-        const volatile unsigned long long* p = fp + t * FLOW_PARTIAL_WORDS;
+    frame_fold<FLOW_WORDS>(fp, n_blocks, lane, [&](const frame_word (&w)[FLOW_WORDS]) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) tot[i] += __longlong_as_double((long long)p[i]);
+        for (int i = 0; i < 6; ++i) tot[i] += word_double(w[i]);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const unsigned long long w = p[6 + i];
-            n[2 * i] += (long long)(w & 0xffffffffull); n[2 * i + 1] += (long long)(w >> 32);
-        }
+        for (int i = 0; i < 3; ++i) { n[2 * i] += (long long)word_lo(w[6 + i]); n[2 * i + 1] += (long long)word_hi(w[6 + i]); }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const unsigned long long w = p[9 + i];
-            r[2 * i] = fmaxf(r[2 * i], __uint_as_float((unsigned)(w & 0xffffffffull)));
-            r[2 * i + 1] = fmaxf(r[2 * i + 1], __uint_as_float((unsigned)(w >> 32)));
-        }
-    }
+        for (int i = 0; i < 2; ++i) { r[2 * i] = fmaxf(r[2 * i], word_lo_f(w[9 + i])); r[2 * i + 1] = fmaxf(r[2 * i + 1], word_hi_f(w[9 + i])); }
+    });
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int i = 0; i < 6; ++i) { tot[i] = wave_sum(tot[i]); n[i] = wave_sum(n[i]); }
 #pragma unroll
-        for (int i = 0; i < 6; ++i) { tot[i] += __shfl_xor(tot[i], o); n[i] += __shfl_xor(n[i], o); }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = fmaxf(r[i], __shfl_xor(r[i], o));
-    }
+    for (int i = 0; i < 4; ++i) r[i] = wave_max(r[i]);
     if (lane == 0) {
         if (a.epe_sums)
             for (int i = 0; i < 6; ++i) { a.epe_sums[f * 6 + i] = tot[i]; a.epe_counts[f * 6 + i] = (int64_t)n[i]; }
         if (a.maxrad)
             for (int i = 0; i < 4; ++i) a.maxrad[f * 4 + i] = r[i];
-        __hip_atomic_store(counters + f, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+        frame_counter_reset(counters + f);
     }
 }
 
@@ -280,18 +250,16 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_colour_kernel(NsffFlowMapsA
 }
 
 inline int64_t flow_blocks(int64_t n_pixels) { return (n_pixels + FLOW_BLOCK_PX - 1) / FLOW_BLOCK_PX; }
-inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
 }  // namespace
 
 extern "C" int64_t nsff_flow_maps_scratch_bytes(int32_t n_frames, int32_t H, int32_t W) {
-    if (n_frames < 1 || H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff) return 0;
-    return align16(4 * (int64_t)n_frames) + 8 * (int64_t)FLOW_PARTIAL_WORDS * n_frames * flow_blocks((int64_t)H * W);
+    return frame_dims_ok(n_frames, H, W) ? frame_scratch_bytes(n_frames, flow_blocks((int64_t)H * W), FLOW_WORDS) : 0;
 }
 
 extern "C" int nsff_flow_maps(const NsffFlowMapsArgs* a, void* stream) {
     if (!a) return NSFF_ERR_NULL;
-    if (a->n_frames < 1 || a->n_frames > 65535 || a->H < 1 || a->W < 1 || (int64_t)a->H * a->W > 0x7fffffff) return NSFF_ERR_INVALID;
+    if (!frame_dims_ok(a->n_frames, a->H, a->W)) return NSFF_ERR_INVALID;
     const bool project = a->xyz[0] || a->xyz[1];
     const bool epe = a->epe_sums || a->epe_counts;
     const bool colour = a->image[0] || a->image[1] || a->gt_image[0] || a->gt_image[1];
@@ -321,12 +289,10 @@ extern "C" int nsff_flow_maps(const NsffFlowMapsArgs* a, void* stream) {
     if (((uintptr_t)a->flow[0] | (uintptr_t)a->flow[1] | (uintptr_t)a->gt[0] | (uintptr_t)a->gt[1]) & 7) return NSFF_ERR_ALIGN;
     if (((uintptr_t)a->xyz[0] | (uintptr_t)a->xyz[1] | (uintptr_t)a->Ps | (uintptr_t)a->ts | (uintptr_t)a->maxrad | (uintptr_t)a->scale) & 3)
         return NSFF_ERR_ALIGN;
-    unsigned* counters = reinterpret_cast<unsigned*>(a->scratch);
-    unsigned long long* partials = a->scratch ? reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(a->scratch) + align16(4 * (int64_t)a->n_frames))
-                                              : nullptr;
+    const FrameScratch s = frame_scratch_split(a->scratch, a->n_frames);
     const dim3 grid((unsigned)flow_blocks((int64_t)a->H * a->W), a->n_frames);
     if (project || reduce)
-        hipLaunchKernelGGL(flow_map_kernel, grid, dim3(FLOW_THREADS), 0, (hipStream_t)stream, *a, reduce ? 1 : 0, counters, partials);
+        hipLaunchKernelGGL(flow_map_kernel, grid, dim3(FLOW_THREADS), 0, (hipStream_t)stream, *a, reduce ? 1 : 0, s.counters, s.partials);
     if (colour)
         hipLaunchKernelGGL(flow_colour_kernel, grid, dim3(FLOW_THREADS), 0, (hipStream_t)stream, *a, a->scale ? a->scale : a->maxrad);
     return nsff_launch_status();

@@ -1,4 +1,4 @@
-"""numpy restatement of nsff_frame_finish (csrc/metrics.hip), one frame at a time, in the number formats eval.py runs in:
+"""numpy restatement of nsff_frame_finish (csrc/frames.hip), one frame at a time, in the number formats eval.py runs in:
 fp32 arrays through numpy's own fp32 operations (eval.py:183-184, 213-214, 222-223; utils/visualization.py:10-15 as
 eval.py's save_depth calls it), the squared errors of metrics.py:6-12 formed in fp32 and added in float64.
 

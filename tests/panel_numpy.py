@@ -1,4 +1,4 @@
-"""numpy restatement of nsff_val_panels (csrc/metrics.hip), one frame at a time, in the number formats the reference's
+"""numpy restatement of nsff_val_panels (csrc/frames.hip), one frame at a time, in the number formats the reference's
 validation step runs in (train.py:209-235 over utils/visualization.py:6-44 and torchvision's make_grid): fp32 arrays through
 numpy's own fp32 operations, the shared chains taken from tests/frame_finish_numpy.py.
 

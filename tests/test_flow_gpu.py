@@ -5,7 +5,8 @@ Shapes (F, H, W): (1, 1, 1) one pixel; (3, 19, 33) the g26 scene -- frames at t 
 and 627 pixels a frame: frames 1 and 2 start off any 16-byte alignment of the points (the dword path of the LDS copy) and off
 4-byte alignment of the images; (2, 37, 71) 2627 pixels, odd: a workgroup covers 1024 pixels, so a frame is two full workgroups
 and a partial one of 579 -- three partials for the frame's last workgroup to add, which is the smallest number at which the
-order of that addition matters.
+order of that addition matters; (2, 129, 511) 65 919 pixels, odd -- 65 workgroups a frame, the last one ragged, so lane 0 of the
+frame's last workgroup folds two partials (blocks 0 and 64) before the butterfly and every other lane one.
 
 Colour images are compared with the twin over EVERY pixel (the radius is the same fp32 operations on both sides, so no pixel
 near radius 1 needs leaving out; only atan2f differs from numpy's): at most one level, at most 1 % of the values."""
@@ -23,8 +24,11 @@ from nsff_pl_amd import _lib, evaluate, flow
 DEV = torch.device("cuda:0")
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [(1, 1, 1), (3, 19, 33), (2, 37, 71)]
-SUM_TOL = 1e-12          # relative: both sides add the same fp32 terms in float64; (n - 1) * 2^-53 < 3e-13 for n <= 2627 terms
+SHAPES = [(1, 1, 1), (3, 19, 33), (2, 37, 71), (2, 129, 511)]
+# relative: both sides add the same fp32 terms in float64, the reference with math.fsum (correctly rounded).  Any order of n
+# non-negative terms is within (n - 1) * 2^-53 < 3e-13 for n <= 2627 terms; at (2, 129, 511) a term passes through at most 21
+# additions on the device (4 in its lane, 6 + 3 in its workgroup, 2 + 6 in the frame's last workgroup): 21 * 2^-53 < 3e-15
+SUM_TOL = 1e-12
 COLOUR_DIFFER = 0.01
 
 
@@ -208,7 +212,7 @@ def test_end_point_error_rule_by_hand(hip_lib):
     assert flow.epe_from_sums(sums, counts).tolist() == [[3.25, 1.5, 5.0]]
 
 
-@pytest.mark.parametrize("shape", [(3, 19, 33), (2, 37, 71)])
+@pytest.mark.parametrize("shape", [(3, 19, 33), (2, 37, 71), (2, 129, 511)])
 def test_a_batch_is_bit_identical_to_single_frames(hip_lib, shape):
     c = case(shape)
     batch = induced(c, shape)

@@ -1,11 +1,13 @@
-"""MI355X checks of nsff_val_panels (csrc/metrics.hip) and the layers on it (panels.validation_panels / error_blend,
+"""MI355X checks of nsff_val_panels (csrc/frames.hip) and the layers on it (panels.validation_panels / error_blend,
 NSFFTrainer.validation_step(panels=...)) against the numpy fp32 restatement tests/panel_numpy.py (itself checked against the
 reference's statements in tests/test_panels_host.py).
 
 Shapes (F, H, W): (1, 1, 1) one pixel, grid only, ma == mi everywhere; (1, 6, 6) the smallest frame SSIM takes; (3, 19, 33) odd
 H * W -- frames 1 and 2 start at flat pixels 627 and 1254, 627 = 156 quads + 3, and GW = 107 is odd, so the 3-byte grid rows land
-at every byte offset; (2, 37, 71) 2627 pixels -- three workgroups, i.e. three partials, a frame.  Tile counts 3, 6, 7, 8; the
-colour tables given (6 and 8 tiles) and NULL (3 and 7)."""
+at every byte offset; (2, 37, 71) 2627 pixels -- three workgroups, i.e. three partials, a frame; (2, 129, 511), with eight tiles
+only, 65 919 pixels -- 65 workgroups a frame, the last one ragged, so lane 0 of the frame's last workgroup folds two partials
+(blocks 0 and 64) before the butterfly; H * W is odd, so frame 0 takes the 16-byte path and frame 1 the element path.  Tile counts
+3, 6, 7, 8; the colour tables given (6 and 8 tiles) and NULL (3 and 7)."""
 import ctypes as C
 import math
 import os
@@ -28,6 +30,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(1, 1, 1), (1, 6, 6), (3, 19, 33), (2, 37, 71)]
 TILES = [3, 6, 7, 8]
+WRAP_SHAPE = (2, 129, 511)
 MAP_TOL = 1e-4           # the project's SSIM map bar
 U8_OUT = ("grid_u8", "rmse_u8", "ssim_u8", "rmse_blend_u8", "ssim_blend_u8")
 
@@ -130,6 +133,10 @@ def test_panels_equal_numpy_exactly(hip_lib, shape, tiles):
         assert not ref["rmse_u8"].any() and ref["grid_u8"].shape == (1, (tiles + 2) // 3 * 3 + 2, 11, 3)
 
 
+def test_panels_equal_numpy_exactly_where_the_fold_wraps(hip_lib):
+    assert_equal(run(WRAP_SHAPE, selection(WRAP_SHAPE, 8)), want(WRAP_SHAPE, 8), f"{WRAP_SHAPE} 8 tiles")
+
+
 # (seeds for which the float64 reference's span is at least 0.05: a condition on the reference alone, asserted below)
 @pytest.mark.parametrize("shape,seed,levels", [((1, 6, 6), 615, 2), ((1, 19, 33), 1933, 1), ((1, 37, 71), 3771, 1)])
 def test_ssim_index_image_end_to_end_bound(hip_lib, shape, seed, levels):
@@ -155,7 +162,7 @@ def test_ssim_index_image_end_to_end_bound(hip_lib, shape, seed, levels):
     assert diff.max() <= bound
 
 
-@pytest.mark.parametrize("shape,tiles", [((3, 19, 33), 8), ((2, 37, 71), 7)])
+@pytest.mark.parametrize("shape,tiles", [((3, 19, 33), 8), ((2, 37, 71), 7), (WRAP_SHAPE, 8)])
 def test_batch_equals_single_frames(hip_lib, shape, tiles):
     batched = run(shape, selection(shape, tiles))
     for f in range(shape[0]):

@@ -1,10 +1,12 @@
-"""MI355X checks of nsff_frame_finish (csrc/metrics.hip) against the numpy fp32 restatement tests/frame_finish_numpy.py (itself
+"""MI355X checks of nsff_frame_finish (csrc/frames.hip) against the numpy fp32 restatement tests/frame_finish_numpy.py (itself
 checked against the reference's statements in tests/test_eval_split_host.py), and of the split layer on top of it
 (evaluate.render_split / SequenceScores / evaluate_split) against the existing render path.
 
 Shapes (F, H, W): (1, 1, 1) one pixel; (3, 19, 33) odd H * W with F > 1 -- frames 1 and 2 start at flat pixels 627 and 1254,
 neither a multiple of four, and 627 = 156 quads + 3; (2, 37, 71) 2627 pixels -- three workgroups, i.e. three partials, a frame;
-(1, 6, 6) the smallest frame SSIM takes."""
+(1, 6, 6) the smallest frame SSIM takes; (2, 129, 511) 65 919 pixels -- 65 workgroups a frame, the last one ragged, so lane 0 of the
+frame's last workgroup folds two partials (blocks 0 and 64) before the butterfly and every other lane one; H * W is odd, so frame 0
+takes the 16-byte path and frame 1 the element path."""
 import numpy as np
 import pytest
 import torch
@@ -16,10 +18,13 @@ from nsff_pl_amd import _lib, evaluate, metrics
 
 DEV = torch.device("cuda:0")
 pytestmark = pytest.mark.gpu
-SHAPES = [(1, 1, 1), (3, 19, 33), (2, 37, 71), (1, 6, 6)]
+SHAPES = [(1, 1, 1), (3, 19, 33), (2, 37, 71), (1, 6, 6), (2, 129, 511)]
 DEPTH_KINDS = {(1, 1, 1): ["plain"], (3, 19, 33): ["nan", "posinf", "negative"], (2, 37, 71): ["constant", "neginf"],
-               (1, 6, 6): ["nan_posinf"]}
-SUM_TOL = 1e-12          # relative: both sides add the same fp32 squares in float64; (n - 1) * 2^-53 < 9e-13 for n <= 7881 terms
+               (1, 6, 6): ["nan_posinf"], (2, 129, 511): ["negative", "nan"]}
+# relative: both sides add the same fp32 squares in float64, the reference with math.fsum (correctly rounded).  Any order of n
+# non-negative terms is within (n - 1) * 2^-53 < 9e-13 for n <= 7881 terms; at (2, 129, 511) a term passes through at most 29
+# additions on the device (12 in its lane, 6 + 3 in its workgroup, 2 + 6 in the frame's last workgroup): 29 * 2^-53 < 4e-15
+SUM_TOL = 1e-12
 PSNR_TOL = 1e-4          # the project's relative bar
 
 
@@ -148,7 +153,7 @@ def test_empty_and_full_masks(hip_lib):
     assert np.isnan(metrics.psnr_frames(gt, rgb)[1].cpu().numpy()).all()
 
 
-@pytest.mark.parametrize("shape", [(3, 19, 33), (2, 37, 71)])
+@pytest.mark.parametrize("shape", [(3, 19, 33), (2, 37, 71), (2, 129, 511)])
 def test_a_batch_is_bit_identical_to_single_frames(hip_lib, shape):
     c = case(shape)
     batch = finish(c)

@@ -74,7 +74,7 @@ def test_c_abi_rejects_bad_arguments_without_a_launch():
     assert lib.nsff_ssim(C.byref(args(map=None, sums=p, scratch=p, scratch_bytes=4)), None) == -1   # too small
     assert lib.nsff_ssim(C.byref(args(map=None, sums=p, scratch=p + 4, scratch_bytes=1 << 20)), None) == -3
     assert lib.nsff_ssim_scratch_bytes(1, 5, 8) == 0 and lib.nsff_ssim_scratch_bytes(0, 8, 8) == 0
-    assert lib.nsff_ssim_scratch_bytes(2, 288, 512) == 16 + 12 * 2 * 8 * 18
+    assert lib.nsff_ssim_scratch_bytes(2, 288, 512) == 16 + 16 * 2 * 8 * 18
     assert lib.nsff_cdf(None, 1, 4, None, None) == -2 and lib.nsff_cdf(None, -1, 4, None, None) == -1
     assert lib.nsff_cdf(None, 0, 4, None, None) == 0
     d = _lib.RayDrawArgs(n_frames=2, n_pixels=64, frame=0, batch=8)

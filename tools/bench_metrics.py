@@ -8,13 +8,13 @@ weights + one fp64 CDF launch); one 1024-ray RayBank.sample() (torch.rand + one 
 pass reads gt + pred (2 x 12 B per pixel) and writes the 4-B weight per pixel; the CDF reads 4 B and writes 8 B per pixel.
 frames.build_records for 100 frames with uint8 images and masks (csrc/rays.hip::ray_records_kernel): the whole call (frame table
 upload + one launch) and the launch alone; it reads 3 + 4 + 1 + 16 B and writes 64 B per pixel.
-metrics.finish_frames on 1 and 100 frames with every input and output (csrc/metrics.hip::frame_image_kernel + frame_depth_kernel):
+metrics.finish_frames on 1 and 100 frames with every input and output (csrc/frames.hip::frame_image_kernel + frame_depth_kernel):
 the whole call (output allocation + two launches) and nsff_frame_finish alone on preallocated outputs.  The image pass reads
 12 + 12 + 1 + 4 B and writes 12 + 3 B per pixel, the depth pass reads 4 B and writes 1 + 3 B: 52 B per pixel.
 flow_frames' kernel work on 1 and 100 frames, both directions with ground truth and mask (csrc/flow.hip::flow_map_kernel +
 flow_colour_kernel): nsff_flow_maps alone on preallocated outputs, its two launches separately, and the projection alone.  Per pixel and direction the
 map pass reads 12 + 8 B and writes 8 B, the colour pass reads 8 + 8 B and writes 3 + 3 B, plus the 1-B mask: 101 B per pixel.
-The validation panels (--only panel) on 1 and 30 frames with all eight tiles (csrc/metrics.hip::panel_range_kernel +
+The validation panels (--only panel) on 1 and 30 frames with all eight tiles (csrc/frames.hip::panel_range_kernel +
 panel_compose_kernel): nsff_val_panels alone on preallocated outputs and its range launch alone.  The range pass reads gt, pred, depth,
 static depth, disp and the SSIM loss map (48 B per pixel); the compose pass reads those again plus alpha, static rgb and mask
 (68 B) and writes the two index images, the two blends and nine grid cells (1 + 1 + 3 + 3 + 27 B): 151 B per pixel.
