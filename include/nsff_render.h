@@ -592,6 +592,56 @@ typedef struct NsffRayRecordArgs {
 } NsffRayRecordArgs;
 int nsff_ray_records(const NsffRayRecordArgs* args, void* stream);
 
+/* ---- resizing decoded frames to the training resolution (csrc/resize.hip): the four resize statements of
+ * the reference's dataset constructor, datasets/monocular.py:98-99, 146-147, 158-163, 168-176 and datasets/flowlib.py:320-338.
+ * A resize is separable: one table per axis says, for each output index, which source indices it reads and with which weights.
+ * The tables are built on the HOST, in double, by nsff_resize_table and applied on the device by nsff_frame_resize.
+ *   NSFF_RESIZE_LANCZOS_U8   PIL Image.resize(.., LANCZOS) on 8-bit pixels: Pillow's precompute_coeffs + normalize_coeffs_8bpc.
+ *                            scale = n_in / n_out, fs = max(scale, 1), support = 3 fs, ksize = 2 ceil(support) + 1; output i:
+ *                            c = (i + 0.5) scale, start = max((int)(c - support + 0.5), 0), count = min((int)(c + support + 0.5),
+ *                            n_in) - start, w_j = L((j + start - c + 0.5) (1 / fs)) with L(x) = sinc(x) sinc(x / 3) on -3 <= x < 3,
+ *                            divided by their sum where that is non-zero, then int32 (int)(+-0.5 + w 2^22) (sign of w), zero-padded
+ *                            to ksize.  Tables wider than NSFF_RESIZE_MAX_KSIZE = 2 ceil(3 * 8) + 1 (a downscale beyond 8x) are
+ *                            NSFF_ERR_UNSUPPORTED; every upscale has ksize 7.
+ *   NSFF_RESIZE_NEAREST_PIL  PIL Image.resize(.., NEAREST): a = n_in / n_out, x = 0.5 a, index = (int)x, x += a (the running sum).
+ *   NSFF_RESIZE_NEAREST_CV   OpenCV resizeNN: min(floor(i * (1 / (n_out / n_in))), n_in - 1).
+ *   NSFF_RESIZE_LINEAR_CV    OpenCV fp32 INTER_LINEAR: fx = (float)((i + 0.5)(n_in / n_out) - 0.5), sx = floor(fx), fx -= sx; sx < 0:
+ *                            sx = 0, fx = 0; sx >= n_in - 1: sx = n_in - 1, fx = 0; taps sx and min(sx + 1, n_in - 1) (count = their
+ *                            number), weights the fp32 pair (1 - fx, fx).
+ * nsff_resize_ksize: weights per output index (1 for the two nearest rules -- they have none --, 2 for linear), or an error.
+ * nsff_resize_table: start, count (n_out) int32 and weights (n_out, ksize) int32 (Lanczos) / fp32 (linear) / unused, NULL allowed
+ * (nearest), all HOST memory; no GPU work. */
+#define NSFF_ERR_UNSUPPORTED     -5   /* a valid request outside what the kernels are built for */
+#define NSFF_RESIZE_LANCZOS_U8    0
+#define NSFF_RESIZE_NEAREST_PIL   1
+#define NSFF_RESIZE_NEAREST_CV    2
+#define NSFF_RESIZE_LINEAR_CV     3
+#define NSFF_RESIZE_MAX_KSIZE    49
+int nsff_resize_ksize(int32_t filter, int32_t n_in, int32_t n_out);
+int nsff_resize_table(int32_t filter, int32_t n_in, int32_t n_out, int32_t* start, int32_t* count, void* weights);
+
+/* n_frames frames (F, src_h, src_w, C) -> (F, dst_h, dst_w, C), channels last, with the DEVICE tables of the two axes.  One launch,
+ * asynchronous on `stream`, no allocation, no synchronisation, no scratch: capturable.
+ *   LANCZOS_U8   uint8, C = 1..3.  Pillow's two 8-bit passes, horizontal first, each acc = 2^21 + sum pixel * k in int32 and
+ *                clamp(acc >> 22, 0, 255); a pass whose size does not change is skipped.  The intermediate image between the
+ *                passes exists only in LDS, as uint8, per output tile.
+ *   NEAREST_PIL  uint8, C = 1..3;  NEAREST_CV  fp32, C = 1..3: dst[y][x] = src[y_start[y]][x_start[x]].
+ *   LINEAR_CV    fp32, C = 1..2: h_r = s[r][x0] wx0 + s[r][x1] wx1 for the two rows, v = h_0 wy0 + h_1 wy1, dst = v * ratio[c];
+ *                every step one fp32 operation (flowlib.resize_flow: ratio = {(float)(w / ws), (float)(h / hs)}).
+ * ksize_x / ksize_y must be nsff_resize_ksize of the axis (else NSFF_ERR_INVALID; beyond the limit NSFF_ERR_UNSUPPORTED);
+ * n_frames <= 65535, 1 <= h * w * C < 2^31 on both sides; a missing pointer is NSFF_ERR_NULL; tables and fp32 images 4-byte
+ * aligned (NSFF_ERR_ALIGN).  Table entries are clamped into the source image on the device. */
+typedef struct NsffFrameResizeArgs {
+    int32_t n_frames, filter, channels, pad_;
+    int32_t src_h, src_w, dst_h, dst_w;
+    int32_t ksize_x, ksize_y;
+    float   ratio[2];           /* LINEAR_CV only                                           */
+    const void* src;  void* dst;
+    const int32_t* x_start;  const int32_t* x_count;  const void* x_weights;     /* (dst_w), (dst_w), (dst_w, ksize_x) */
+    const int32_t* y_start;  const int32_t* y_count;  const void* y_weights;     /* (dst_h), (dst_h), (dst_h, ksize_y) */
+} NsffFrameResizeArgs;
+int nsff_frame_resize(const NsffFrameResizeArgs* args, void* stream);
+
 /* ---- a6: eval-only frustum visibility (reference rendering.py:190-200 with datasets/ray_utils.py:127-151,154-181) ---- */
 typedef struct NsffFrustumArgs {
     const float*   w2c;         /* device (n_cams * n_frames, 12): row-major first three rows of inverse([c2w; 0 0 0 1]),

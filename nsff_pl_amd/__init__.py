@@ -12,7 +12,8 @@ from .range_check import RangeFlags, range_flags
 from .nerf import NeRF, PosEmbedding
 from .rendering import render_rays, sample_pdf
 from .interpolation import interpolate
-from .frames import build_records, projection_matrices
+from .frames import (build_records, projection_matrices, resize_images, resize_masks, resize_disps, resize_flows, resize_frames,
+                     scaled_intrinsics)
 from .sampling import RayBank
 from . import flow
 from .flow import induced_flow, flow_to_image, flow_epe, epe_from_sums
@@ -22,5 +23,6 @@ from .panels import validation_panels, error_blend
 __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "set_precision", "get_precision",
            "set_range_check", "get_range_check", "range_flags", "RangeFlags",
            "build_records", "projection_matrices", "RayBank",
+           "resize_images", "resize_masks", "resize_disps", "resize_flows", "resize_frames", "scaled_intrinsics",
            "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
            "panels", "validation_panels", "error_blend"]

@@ -21,7 +21,8 @@ MAX_FREQS = 24
 _ERR = {-1: "NSFF_ERR_INVALID (bad shape/flag/unsupported architecture)",
         -2: "NSFF_ERR_NULL (required pointer missing)",
         -3: "NSFF_ERR_ALIGN (pointer not 16-byte aligned)",
-        -4: "NSFF_ERR_HIP"}
+        -4: "NSFF_ERR_HIP",
+        -5: "NSFF_ERR_UNSUPPORTED (a valid request outside what the kernels are built for)"}
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -218,6 +219,18 @@ class RayRecordArgs(C.Structure):
                 ("frame_table", _fp), ("records", _fp)]
 
 
+RESIZE_LANCZOS_U8, RESIZE_NEAREST_PIL, RESIZE_NEAREST_CV, RESIZE_LINEAR_CV = range(4)      # NSFF_RESIZE_*
+RESIZE_MAX_KSIZE = 49
+ERR_UNSUPPORTED = -5
+
+
+class FrameResizeArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("filter", C.c_int32), ("channels", C.c_int32), ("pad_", C.c_int32),
+                ("src_h", C.c_int32), ("src_w", C.c_int32), ("dst_h", C.c_int32), ("dst_w", C.c_int32),
+                ("ksize_x", C.c_int32), ("ksize_y", C.c_int32), ("ratio", C.c_float * 2), ("src", _fp), ("dst", _fp),
+                ("x_start", _fp), ("x_count", _fp), ("x_weights", _fp), ("y_start", _fp), ("y_count", _fp), ("y_weights", _fp)]
+
+
 # name -> (restype, argtypes); also the list of symbols the header declares
 _SIGNATURES = {
     "nsff_abi_version": (C.c_int, []),
@@ -253,6 +266,9 @@ _SIGNATURES = {
     "nsff_frame_rays": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float,
                                   C.c_float, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_records": (C.c_int, [C.POINTER(RayRecordArgs), _fp]),
+    "nsff_resize_ksize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_resize_table": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nsff_frame_resize": (C.c_int, [C.POINTER(FrameResizeArgs), _fp]),
     "nsff_bwd_packed_bytes": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_size_t)]),
     "nsff_pack_weights_bwd": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(_fp), _fp, _fp]),
     "nsff_field_backward": (C.c_int, [C.POINTER(ModelDesc), _fp, C.POINTER(FieldBwdArgs), _fp]),
@@ -1264,6 +1280,54 @@ def ray_records(K4, frame_table, images, disps, masks, flow_fw, flow_bw, near, f
                       records=_dptr(records, torch.float32, "ray_records: out"))
     with torch.cuda.device(records.device):
         _check(load().nsff_ray_records(C.byref(a), _stream()), "nsff_ray_records")
+
+
+def resize_ksize(filter, n_in, n_out):
+    """nsff_resize_ksize: weights per output index of the table, or the (negative) error code."""
+    return int(load().nsff_resize_ksize(int(filter), int(n_in), int(n_out)))
+
+
+def resize_table(filter, n_in, n_out):
+    """nsff_resize_table on the host: (start (n_out) int32, count (n_out) int32, weights (n_out, ksize) int32 / fp32 or None) as
+    CPU tensors.  A Lanczos table wider than RESIZE_MAX_KSIZE (a downscale beyond 8x) is refused."""
+    filter, n_in, n_out = int(filter), int(n_in), int(n_out)
+    ksize = resize_ksize(filter, n_in, n_out)
+    if ksize == ERR_UNSUPPORTED:
+        raise RuntimeError(f"resize: {n_in} -> {n_out} is a {n_in / n_out:.2f}x downscale; the Lanczos kernel holds tables up to "
+                           f"{RESIZE_MAX_KSIZE} taps, a downscale of at most 8x")
+    if ksize < 0:
+        _check(ksize, "nsff_resize_ksize")
+    start, count = torch.empty(n_out, dtype=torch.int32), torch.empty(n_out, dtype=torch.int32)
+    weights = None
+    if filter in (RESIZE_LANCZOS_U8, RESIZE_LINEAR_CV):
+        weights = torch.empty(n_out, ksize, dtype=torch.int32 if filter == RESIZE_LANCZOS_U8 else torch.float32)
+    _check(load().nsff_resize_table(filter, n_in, n_out, start.data_ptr(), count.data_ptr(),
+                                    None if weights is None else weights.data_ptr()), "nsff_resize_table")
+    return start, count, weights
+
+
+def frame_resize(filter, src, dst, x_table, y_table, ratio=(1.0, 1.0)):
+    """nsff_frame_resize: src (F, h, w, C) -> dst (F, H, W, C), contiguous GPU tensors, uint8 (LANCZOS_U8, NEAREST_PIL) or fp32;
+    x_table / y_table: resize_table()'s triples for (w -> W) and (h -> H) on the same device."""
+    filter = int(filter)
+    dtype = torch.uint8 if filter in (RESIZE_LANCZOS_U8, RESIZE_NEAREST_PIL) else torch.float32
+    F, h, w, ch = (int(v) for v in src.shape)
+    if dst.dim() != 4 or int(dst.shape[0]) != F or int(dst.shape[3]) != ch or dst.device != src.device:
+        raise RuntimeError(f"frame_resize: dst {tuple(dst.shape)} on {dst.device} does not go with src {tuple(src.shape)} on {src.device}")
+    H, W = int(dst.shape[1]), int(dst.shape[2])
+    a = FrameResizeArgs(n_frames=F, filter=filter, channels=ch, src_h=h, src_w=w, dst_h=H, dst_w=W,
+                        src=_dptr(src, dtype, "frame_resize: src"), dst=_dptr(dst, dtype, "frame_resize: dst"))
+    a.ratio[0], a.ratio[1] = float(ratio[0]), float(ratio[1])
+    wdtype = torch.int32 if filter == RESIZE_LANCZOS_U8 else torch.float32
+    for axis, (start, count, weights), n in (("x", x_table, W), ("y", y_table, H)):
+        if start.numel() != n or count.numel() != n or start.device != src.device:
+            raise RuntimeError(f"frame_resize: the {axis} table has {start.numel()} entries on {start.device}, expected {n} on {src.device}")
+        setattr(a, f"{axis}_start", _dptr(start, torch.int32, f"frame_resize: {axis}_start"))
+        setattr(a, f"{axis}_count", _dptr(count, torch.int32, f"frame_resize: {axis}_count"))
+        setattr(a, f"{axis}_weights", _dptr(weights, wdtype, f"frame_resize: {axis}_weights"))
+        setattr(a, f"ksize_{axis}", 1 if weights is None else int(weights.shape[1]))
+    with torch.cuda.device(src.device):
+        _check(load().nsff_frame_resize(C.byref(a), _stream()), "nsff_frame_resize")
 
 
 def range_flags(out, clear):

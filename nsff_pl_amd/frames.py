@@ -1,14 +1,20 @@
 """From decoded frames to what a training run needs: the ray bank's records and the loss's projection matrices.
 
 The reference builds both in its dataset constructor (datasets/monocular.py:127-187), frame by frame on the CPU, after it has
-decoded and resized the files.  Decoding and resizing stay with the caller; everything after them is here:
+decoded and resized the files.  Decoding stays with the caller; everything after it is here:
 
+* :func:`resize_frames`       -- the reference's four resize statements on decoded frames at their native sizes
+                                 (``nsff_frame_resize``, one launch per kind): :func:`resize_images` PIL's 8-bit LANCZOS byte
+                                 for byte, :func:`resize_masks` PIL's NEAREST, :func:`resize_disps` cv2's INTER_NEAREST,
+                                 :func:`resize_flows` ``flowlib.resize_flow``; :func:`scaled_intrinsics` is the K that goes
+                                 with them (monocular.py:61-65).  The per-axis tables are built on the host once per
+                                 (filter, n_in, n_out) and kept per device;
 * :func:`projection_matrices` -- ``Ks`` (1,3,3) and ``Ps`` (1,F,3,4), monocular.py:127-134, on the host in float64;
 * :func:`build_records`       -- the (F, H*W, 16) records of monocular.py:136-184 for all frames in ONE launch
                                  (``nsff_ray_records``): NDC rays (the arithmetic of :func:`evaluate.frame_rays`, bit for bit),
                                  rgb, t, disparity, mask, ``uv + flow_fw``, ``uv + flow_bw``.
 
-Inputs are GPU tensors already at the target resolution, channels LAST: images (F,H,W,3) uint8 or fp32 in [0,1], disparities
+:func:`build_records`' inputs are GPU tensors at the target resolution (what :func:`resize_frames` returns), channels LAST: images (F,H,W,3) uint8 or fp32 in [0,1], disparities
 (F,H,W) fp32, masks (F,H,W) uint8 or fp32, flows (F,H,W,2) fp32 in pixels.  uint8 values are divided by 255 on the device, as
 torchvision's ``ToTensor`` does.  ``sampling.RayBank.from_frames`` wraps both functions.
 """
@@ -107,3 +113,114 @@ def build_records(K, poses, images, disps, masks, flows_fw=None, flows_bw=None, 
                      masks.contiguous(), None if flows_fw is None else flows_fw.contiguous(),
                      None if flows_bw is None else flows_bw.contiguous(), near, first_frame, count, out)
     return out
+
+
+# ---- resizing decoded frames to the training resolution (csrc/resize.hip) ----
+_TABLES = {}                    # (device, filter, n_in, n_out) -> (start, count, weights) on that device
+
+
+def _table(dev, filt, n_in, n_out):
+    """The (filter, n_in, n_out) table of one axis on `dev`: built once on the host (nsff_resize_table), then kept."""
+    key = (str(dev), int(filt), int(n_in), int(n_out))
+    if key not in _TABLES:
+        _TABLES[key] = tuple(None if t is None else t.to(dev) for t in _lib.resize_table(filt, n_in, n_out))
+    return _TABLES[key]
+
+
+def _wh(img_wh, who):
+    if not isinstance(img_wh, (tuple, list)) or len(img_wh) != 2 or not all(isinstance(v, (int, np.integer)) and v >= 1 for v in img_wh):
+        raise ValueError(f"{who}: img_wh must be (width, height), two positive integers, got {img_wh!r}")
+    return int(img_wh[0]), int(img_wh[1])
+
+
+def _resize_stack(x, what, who):
+    """One input kind as a stacked tensor: a list of per-frame tensors (all of one size) is stacked, one copy."""
+    if isinstance(x, (list, tuple)):
+        if not x or not all(isinstance(f, torch.Tensor) for f in x):
+            raise TypeError(f"{who}: every entry of the {what} list must be a tensor")
+        if len({tuple(f.shape) for f in x}) != 1:
+            raise ValueError(f"{who}: the frames of the {what} list differ in shape: {sorted({tuple(f.shape) for f in x})}")
+        x = torch.stack(list(x))
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{who}: {what} must be a tensor or a list of per-frame tensors")
+    _lib.require_gpu_tensor(x, f"{who}: {what}")
+    return x
+
+
+def _resize(x, img_wh, filt, dtype, channels, what, who):
+    """x (F, h, w[, C]) -> (F, H, W[, C]) with filter `filt`; an input already at img_wh comes back as a copy."""
+    W, H = _wh(img_wh, who)
+    x = _resize_stack(x, what, who)
+    want = 3 if channels is None else 4
+    if x.dim() != want or (channels is not None and x.shape[-1] not in channels):
+        hint = ""
+        if channels is not None and x.dim() == 4 and x.shape[1] in channels:
+            hint = f" -- this looks channels-first (F,{x.shape[1]},h,w): permute(0, 2, 3, 1) it"
+        shape = "(F,h,w)" if channels is None else f"(F,h,w,C) with C in {tuple(channels)}"
+        raise ValueError(f"{who}: {what} must be channels-last {shape}, got {tuple(x.shape)}{hint}")
+    if x.dtype != dtype:
+        extra = " (the Lanczos rule is Pillow's 8-bit one: resize the decoded bytes, not ToTensor's floats)" if filt == _lib.RESIZE_LANCZOS_U8 else ""
+        raise TypeError(f"{who}: {what} must be {dtype}, got {x.dtype}{extra}")
+    F, h, w = (int(v) for v in x.shape[:3])
+    if (w, h) == (W, H):
+        return x.clone(memory_format=torch.contiguous_format)
+    xt, yt = _table(x.device, filt, w, W), _table(x.device, filt, h, H)
+    src = x.contiguous().reshape(F, h, w, -1)
+    out = torch.empty((F, H, W) + tuple(x.shape[3:]), dtype=dtype, device=x.device)
+    ratio = (np.float32(W / w), np.float32(H / h)) if filt == _lib.RESIZE_LINEAR_CV else (1.0, 1.0)
+    _lib.frame_resize(filt, src, out.view(F, H, W, -1), xt, yt, ratio)
+    return out
+
+
+def resize_images(images, img_wh):
+    """(F,h,w,C) uint8, C = 3 (or 1) -> (F,H,W,C) uint8 with img_wh = (W, H): PIL's ``img.resize(img_wh, Image.LANCZOS)``
+    (monocular.py:146-147) byte for byte, both 8-bit passes in one launch.  Downscales up to 8x, any upscale."""
+    return _resize(images, img_wh, _lib.RESIZE_LANCZOS_U8, torch.uint8, (1, 3), "images", "resize_images")
+
+
+def resize_masks(masks, img_wh):
+    """(F,h,w) uint8 -> (F,H,W) uint8: PIL's ``mask.resize(img_wh, Image.NEAREST)`` (monocular.py:162-163)."""
+    return _resize(masks, img_wh, _lib.RESIZE_NEAREST_PIL, torch.uint8, None, "masks", "resize_masks")
+
+
+def resize_disps(disps, img_wh):
+    """(F,h,w) fp32 -> (F,H,W) fp32: ``cv2.resize(disp, img_wh, interpolation=cv2.INTER_NEAREST)`` (monocular.py:158-159)."""
+    return _resize(disps, img_wh, _lib.RESIZE_NEAREST_CV, torch.float32, None, "disps", "resize_disps")
+
+
+def resize_flows(flows, img_wh):
+    """(F,h,w,2) fp32 -> (F,H,W,2) fp32: ``flowlib.resize_flow(flow, W, H)`` -- cv2's bilinear resize, then u *= W/w, v *= H/h
+    (flowlib.py:320-338).  None passes through."""
+    if isinstance(flows, (list, tuple)):                        # build_records' convention: a None entry is a frame without flow
+        some = next((f for f in flows if f is not None), None)
+        flows = None if some is None else [torch.zeros_like(some) if f is None else f for f in flows]
+    if flows is None:
+        return None
+    return _resize(flows, img_wh, _lib.RESIZE_LINEAR_CV, torch.float32, (2,), "flows", "resize_flows")
+
+
+def resize_frames(images, disps, masks, flows_fw=None, flows_bw=None, img_wh=None):
+    """Decoded frames at their native sizes -> the dict ``build_records(K, poses, **d)`` takes, everything at img_wh = (W, H).
+    Each kind may have its own source size; inputs are stacked GPU tensors or lists of per-frame tensors, channels last."""
+    if img_wh is None:
+        raise ValueError("resize_frames: img_wh = (width, height) is required")
+    return dict(images=resize_images(images, img_wh), disps=resize_disps(disps, img_wh), masks=resize_masks(masks, img_wh),
+                flows_fw=resize_flows(flows_fw, img_wh), flows_bw=resize_flows(flows_bw, img_wh))
+
+
+def scaled_intrinsics(K_or_f, src_wh, img_wh):
+    """(3,3) fp32 intrinsics at img_wh from the calibration at src_wh = (W, H), monocular.py:61-65: a focal length f gives
+    [[f,0,W/2],[0,f,H/2],[0,0,1]] in fp32; a (3,3) K is taken as it is; then row 0 *= w/W and row 1 *= h/H."""
+    (W, H), (w, h) = _wh(src_wh, "scaled_intrinsics"), _wh(img_wh, "scaled_intrinsics")
+    if isinstance(K_or_f, torch.Tensor):
+        K_or_f = K_or_f.detach().cpu().numpy()
+    if np.ndim(K_or_f) == 0:
+        f = float(K_or_f)
+        K = np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], dtype=np.float32)
+    else:
+        K = np.array(K_or_f, dtype=np.float32)
+        if K.shape != (3, 3):
+            raise ValueError(f"scaled_intrinsics: K must be (3,3) or a focal length, got {K.shape}")
+    K[0] *= w / W
+    K[1] *= h / H
+    return torch.from_numpy(K)

@@ -58,11 +58,16 @@ class RayBank:
         self.Ks = self.Ps = None                                         # set by from_frames (monocular.py:127-134)
 
     @classmethod
-    def from_frames(cls, K, poses, images, disps, masks, flows_fw, flows_bw, img_wh, hard_sampling=False, seed=None):
+    def from_frames(cls, K, poses, images, disps, masks, flows_fw, flows_bw, img_wh, hard_sampling=False, seed=None, resize=False):
         """The bank of decoded frames (GPU tensors at the target resolution, see :func:`frames.build_records`): the records
         come from one launch, and ``Ks`` (1,3,3) / ``Ps`` (1,F,3,4) are what the loss projects with, so
-        ``NSFFTrainer(..., Ks=bank.Ks, Ps=bank.Ps, ray_bank=bank)`` is the whole set-up."""
+        ``NSFFTrainer(..., Ks=bank.Ks, Ps=bank.Ps, ray_bank=bank)`` is the whole set-up.  ``resize=True``: the frames come at
+        their native sizes and go through :func:`frames.resize_frames` to img_wh first (K is the one at img_wh:
+        :func:`frames.scaled_intrinsics`)."""
         from . import frames
+        if resize:
+            d = frames.resize_frames(images, disps, masks, flows_fw, flows_bw, img_wh)
+            images, disps, masks, flows_fw, flows_bw = d["images"], d["disps"], d["masks"], d["flows_fw"], d["flows_bw"]
         records = frames.build_records(K, poses, images, disps, masks, flows_fw, flows_bw)
         bank = cls(records, img_wh, hard_sampling=hard_sampling, seed=seed)
         Ks, Ps = frames.projection_matrices(K, poses)

@@ -18,6 +18,10 @@ The validation panels (--only panel) on 1 and 30 frames with all eight tiles (cs
 panel_compose_kernel): nsff_val_panels alone on preallocated outputs and its range launch alone.  The range pass reads gt, pred, depth,
 static depth, disp and the SSIM loss map (48 B per pixel); the compose pass reads those again plus alpha, static rgb and mask
 (68 B) and writes the two index images, the two blends and nine grid cells (1 + 1 + 3 + 3 + 27 B): 151 B per pixel.
+The frame resize (--only resize) of 1 and 30 decoded 1280 x 720 frames to 512 x 288 (csrc/resize.hip): each kernel of
+nsff_frame_resize alone on preallocated outputs with the tables already on the device -- Lanczos on uint8 RGB, nearest on the
+uint8 mask and the fp32 disparity, bilinear on the fp32 flow.  Byte bound: every source byte read once plus every output byte
+written (the nearest kernels read fewer: a source pixel they skip is never touched, so their bound is an upper one).
 """
 import argparse
 import json
@@ -150,10 +154,25 @@ def bench_panels(dev, g, W, H, reps, F):
             f"panel_range_F{F}_bound_us": px * PANEL_RANGE_BYTES_PER_PIXEL / HBM_PEAK * 1e6}
 
 
+def bench_resize(dev, g, W, H, reps, F, src_wh=(1280, 720)):
+    w, h = src_wh
+    cases = (("lanczos_rgb", _lib.RESIZE_LANCZOS_U8, torch.randint(0, 256, (F, h, w, 3), device=dev, generator=g, dtype=torch.uint8)),
+             ("nearest_mask", _lib.RESIZE_NEAREST_PIL, torch.randint(0, 256, (F, h, w, 1), device=dev, generator=g, dtype=torch.uint8)),
+             ("nearest_disp", _lib.RESIZE_NEAREST_CV, torch.rand(F, h, w, 1, device=dev, generator=g)),
+             ("linear_flow", _lib.RESIZE_LINEAR_CV, torch.randn(F, h, w, 2, device=dev, generator=g)))
+    res = {}
+    for name, filt, src in cases:
+        dst = torch.empty(F, H, W, src.shape[3], dtype=src.dtype, device=dev)
+        xt, yt = frames._table(dev, filt, w, W), frames._table(dev, filt, h, H)
+        res[f"resize_{name}_F{F}_us"] = time_us(lambda: _lib.frame_resize(filt, src, dst, xt, yt, (W / w, H / h)), reps)
+        res[f"resize_{name}_F{F}_bound_us"] = (src.numel() * src.element_size() + dst.numel() * dst.element_size()) / HBM_PEAK * 1e6
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel (default: everything)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize (default: everything)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -171,6 +190,10 @@ def main():
         if "panel" in only:
             for F in (1, 30):
                 out.update(bench_panels(dev, g, W, H, args.reps, F))
+        if "resize" in only:
+            for F in (1, 30):
+                out.update(bench_resize(dev, g, W, H, args.reps, F))
+                torch.cuda.empty_cache()
         print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
         return
     gt = torch.rand(H, W, 3, device=dev, generator=g)
@@ -195,6 +218,7 @@ def main():
         torch.cuda.empty_cache()
     for F in (1, 30):
         out.update(bench_panels(dev, g, W, H, args.reps, F))
+        out.update(bench_resize(dev, g, W, H, args.reps, F))
     print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
 
 
