@@ -971,6 +971,23 @@ int         nsff_last_field_kernel(void);
  * trunk phase of the current one and its point by the body's first instructions.  Results are bit-identical to the one-workgroup-per-tile form (environment
  * NSFF_NO_PERSIST=1, read per launch, selects that form for A/B measurements). */
 int         nsff_last_field_grid(void);
+/* The MFMA shape of the hand-scheduled inference kernel's trunk phases.  nsff_field_kernel_h3a multiplies with
+ * v_mfma_f32_32x32x16_f16; nsff_field_kernel_h3a16 runs the same schedule, phase programs and arguments on v_mfma_f32_16x16x32_f16
+ * and reads a second packed buffer: the f16x3 pack with the trunk segments' 16-byte chunks in that operand's order
+ * (nsff_repack_field_weights; same size, same offsets, everything but the trunk segments copied).  It covers the inference launches
+ * of models without the view-direction branch (kernel codes NSFF_KERNEL_H3A / _TBIAS, unchanged), whatever their size or form, and
+ * is what nsff_field_query_repacked runs there; nsff_field_query, which has no second buffer, runs the 32 shape.  Environment
+ * NSFF_H3A_SHAPE=16 | 32, read per launch, forces either.  Records differ between the shapes in fp32 summation order only.
+ *   nsff_field_mfma_shape       host-only: the shape nsff_field_query_repacked would run these arguments on (16 or 32; < 0: error)
+ *   nsff_repack_field_weights   asynchronous on `stream`: repacked <- packed (nsff_packed_bytes of the f16x3 pack, 16-byte aligned)
+ *   nsff_field_query_repacked   nsff_field_query given both buffers; a launch planned for shape 16 through nsff_field_query, which
+ *                               has no second buffer, returns NSFF_ERR_NULL instead of running another kernel
+ *   nsff_last_field_mfma_shape  the shape of the last f16x3 launch of this process (0: none yet) */
+int         nsff_field_mfma_shape(const NsffModelDesc* desc, const NsffFieldArgs* args);
+int         nsff_repack_field_weights(const NsffModelDesc* desc, const void* packed, void* repacked, void* stream);
+int         nsff_field_query_repacked(const NsffModelDesc* desc, const void* packed, const void* repacked, const NsffFieldArgs* args,
+                                      void* stream);
+int         nsff_last_field_mfma_shape(void);
 /* Host-only (no GPU work): the f16x3 step program of an inference launch with these modes -- steps[n][4] = {weight segment
  * offset (words), bias offset (words; 0xFFFFFFFF = accumulate), nks | pre << 8 | post << 16 | head << 24, 0} -- and the phase
  * programs (8-dword descriptors, 36 at most per trunk) the hand-scheduled kernel would execute for its static / dynamic trunk;

@@ -237,6 +237,10 @@ _SIGNATURES = {
     "nsff_range_flags": (C.c_int, [_fp, C.c_int32, _fp]),
     "nsff_last_field_kernel": (C.c_int, []),
     "nsff_last_field_grid": (C.c_int, []),
+    "nsff_field_mfma_shape": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(FieldArgs)]),
+    "nsff_repack_field_weights": (C.c_int, [C.POINTER(ModelDesc), _fp, _fp, _fp]),
+    "nsff_field_query_repacked": (C.c_int, [C.POINTER(ModelDesc), _fp, _fp, C.POINTER(FieldArgs), _fp]),
+    "nsff_last_field_mfma_shape": (C.c_int, []),
     "nsff_field_phase_program": (C.c_int, [C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int),
                                    C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "nsff_field_launch_plan": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(FieldArgs), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
@@ -516,6 +520,13 @@ def field_query(model, raw, n_points, pts_per_ray, static_mode, transient_mode, 
         a.t_bias, a.t_bias_rows = _ptr(t_bias), int(t_bias.shape[1])
     if s_bias is not None:                      # (n_rays, 1, 256) from side_bias(): [dir | a]'s part of static_dir_encoding
         a.s_bias, a.s_bias_rows = _ptr(s_bias), int(s_bias.shape[1])
+    # the 16x16x32 form of the hand-scheduled inference kernel -- the default where it covers the launch -- reads a second buffer, built
+    # at the first launch that is planned for it (NSFF_H3A_SHAPE is read per launch; 32: nothing is asked and nothing is built)
+    if os.environ.get("NSFF_H3A_SHAPE") != "32" and prec == config.PRECISIONS["f16x3"] and not saves and \
+            load().nsff_field_mfma_shape(C.byref(desc), C.byref(a)) == 16:
+        _check(load().nsff_field_query_repacked(C.byref(desc), _ptr(packed), _ptr(model.packed(REPACKED)), C.byref(a), _stream()),
+               "nsff_field_query_repacked")
+        return
     _check(load().nsff_field_query(C.byref(desc), _ptr(packed), C.byref(a), _stream()), "nsff_field_query")
 
 
@@ -777,6 +788,18 @@ def frame_rays(K4, c2w12, H, W, near, shift_near, first, count, rays):
     m = (C.c_float * 12)(*[float(v) for v in c2w12])
     _check(load().nsff_frame_rays(k, m, int(H), int(W), float(near), float(shift_near), int(first), int(count),
                                   _ptr(rays), _stream()), "nsff_frame_rays")
+
+
+REPACKED = 101          # PackCache key of the f16x3 pack in the 16x16x32 operand order (nsff_repack_field_weights)
+
+
+def repack_weights(desc, packed, repacked):
+    _check(load().nsff_repack_field_weights(C.byref(desc), _ptr(packed), _ptr(repacked), _stream()), "nsff_repack_field_weights")
+
+
+def last_field_mfma_shape():
+    """16 or 32: the MFMA shape of the trunk phases of the last f16x3 field launch (include/nsff_render.h)."""
+    return int(load().nsff_last_field_mfma_shape())
 
 
 BWD_PACK = 100          # PackCache key of the transposed fp16 weight pack (nsff_pack_weights_bwd)

@@ -593,7 +593,7 @@ int nsff_posenc(const float* x, int64_t n_rows, const float* freqs_host, int n_f
     return e == hipSuccess ? NSFF_OK : nsff_hip_fail(e);
 }
 
-int nsff_field_query(const NsffModelDesc* desc, const void* packed_v, const NsffFieldArgs* args, void* stream) {
+static int field_query(const NsffModelDesc* desc, const void* packed_v, const void* repacked, const NsffFieldArgs* args, void* stream) {
     const float* packed = reinterpret_cast<const float*>(packed_v);
     if (!desc || !packed || !args) return NSFF_ERR_NULL;
     const NsffModelDesc& d = *desc;
@@ -660,7 +660,8 @@ int nsff_field_query(const NsffModelDesc* desc, const void* packed_v, const Nsff
     }
     hipError_t e = hipSuccess;
     if (g.precision == NSFF_PREC_F16X3) {
-        const int rc3 = nsff_h3_field_query(desc, packed_v, args, g.tile_points ? g.tile_points : nsff_h3_default_tile(g.n_points), st, span);
+        const int rc3 = nsff_h3_field_query(desc, packed_v, args, g.tile_points ? g.tile_points : nsff_h3_default_tile(g.n_points), st, span,
+                                            repacked);
         if (rc3 != NSFF_OK) return rc3;
     } else {
         hipLaunchKernelGGL(nsff_field_kernel, dim3((unsigned)tiles), dim3(NTHREADS), 0, st, k);
@@ -684,6 +685,25 @@ int nsff_field_query(const NsffModelDesc* desc, const void* packed_v, const Nsff
     }
     return e == hipSuccess ? NSFF_OK : nsff_hip_fail(e);
 }
+
+int nsff_field_query(const NsffModelDesc* desc, const void* packed, const NsffFieldArgs* args, void* stream) {
+    return field_query(desc, packed, nullptr, args, stream);
+}
+int nsff_field_query_repacked(const NsffModelDesc* desc, const void* packed, const void* repacked, const NsffFieldArgs* args, void* stream) {
+    if (!repacked) return NSFF_ERR_NULL;
+    return field_query(desc, packed, repacked, args, stream);
+}
+int nsff_repack_field_weights(const NsffModelDesc* desc, const void* packed, void* repacked, void* stream) {
+    if (!desc || !packed || !repacked) return NSFF_ERR_NULL;
+    if (((uintptr_t)packed | (uintptr_t)repacked) & 15) return NSFF_ERR_ALIGN;
+    return nsff_h3_repack_weights(desc, packed, repacked, (hipStream_t)stream);
+}
+int nsff_field_mfma_shape(const NsffModelDesc* desc, const NsffFieldArgs* args) {
+    if (!desc || !args) return NSFF_ERR_NULL;
+    if (args->precision != NSFF_PREC_F16X3 || args->n_points <= 0) return 32;
+    return nsff_h3_field_mfma_shape(desc, args);
+}
+int nsff_last_field_mfma_shape(void) { return g_nsff_last_h3_shape; }
 
 int nsff_last_field_kernel(void) { return g_last_field_kernel; }
 int nsff_last_field_grid(void) { return g_last_field_grid; }

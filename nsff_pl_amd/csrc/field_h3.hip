@@ -1074,6 +1074,13 @@ __device__ __forceinline__ float fast_tanh(float v) {
 #else
 #include "field_h3a_body.inc"
 #endif
+// H3A16_BODY: the same schedule on v_mfma_f32_16x16x32_f16 (gen.py: build(shape=16)) -- the body of nsff_field_kernel_h3a16, which reads
+// the trunk segments in the 16-shape order (nsff_repack_kernel_h3a16); everything else of the kernel is shared.
+#ifdef H3_TIMING
+#include "field_h3a16_body_timing.inc"
+#else
+#include "field_h3a16_body.inc"
+#endif
 // The heads evaluated on a trunk's last activation (HEAD_* of its last step): tile / bias offsets in the packed buffer (words),
 // rows, first float of the raw record, activation kinds (two bits per row).
 struct H3AHeadSel { uint32_t w_off, b_off; int n_rows, slot0; unsigned kinds; };
@@ -1249,8 +1256,9 @@ __device__ __forceinline__ H3AKernArgs* h3a_args() {
     return p;
 }
 
-template <bool SAVE>
+template <bool SAVE, int SHAPE = 32>
 __device__ __forceinline__ void h3a_kernel() {
+    static_assert(SHAPE == 32 || (SHAPE == 16 && !SAVE), "the 16-shape body is an inference body");
     constexpr int M = 128, THREADS = 256;
     __shared__ __attribute__((aligned(16))) _Float16 sX[2 * M * LDH];
     __shared__ __attribute__((aligned(16))) float sRaw[M * NSFF_RAW_STRIDE];
@@ -1523,6 +1531,17 @@ __device__ __forceinline__ void h3a_kernel() {
                            [act] "s"(sv_act), [mask] "s"(sv_mask), [astride] "s"(sv_astride), [mstride] "s"(sv_mstride),
                            [rflag] "s"(rflag), [rm0] "v"(rm)
                          : H3A_SAVE_CLOBBERS);
+        } else if constexpr (SHAPE == 16) {
+        asm volatile(H3A16_BODY
+                     : [nx0] "=&v"(px[0]), [nx1] "=&v"(px[1]), [nx2] "=&v"(px[2]), [tid] "+v"(tid_)
+                     : [nxa] "v"(nxa), [pk] "s"(pkb),
+#ifdef H3_TIMING
+                       [dbg] "s"(dbg),
+#endif
+                       [phases] "s"(phases), [lds] "s"(lds), [biaslds] "s"(biaslds), [rawlds] "s"((unsigned)(uintptr_t)sRaw),
+                       [wave] "s"(wave_id), [in_t] "s"(in_t), [tpa0] "v"(tpa0), [tpa1] "v"(tpa1), [tpb0] "v"(tpb0), [tpb1] "v"(tpb1),
+                       [rflag] "s"(rflag), [rm0] "v"(rm)
+                     : H3A16_CLOBBERS);
         } else {
         asm volatile(H3A_BODY
                      : [nx0] "=&v"(px[0]), [nx1] "=&v"(px[1]), [nx2] "=&v"(px[2]), [tid] "+v"(tid_)
@@ -1598,6 +1617,7 @@ __device__ __forceinline__ void h3a_kernel() {
 
 __global__ __launch_bounds__(256, 1) void nsff_field_kernel_h3a(const H3AArgs) { h3a_kernel<false>(); }
 __global__ __launch_bounds__(256, 1) void nsff_field_kernel_h3a_save(const H3AArgs) { h3a_kernel<true>(); }
+__global__ __launch_bounds__(256, 1) void nsff_field_kernel_h3a16(const H3AArgs) { h3a_kernel<false, 16>(); }
 
 // Phase program of one trunk = steps [s0, s1) of the step program (see tools/h3asm/check.py::build_program, the reference
 // implementation of this function, which the simulator runs).  Returns false when the trunk's structure is not one the body
@@ -1934,6 +1954,61 @@ int nsff_h3_pack_weights(const NsffModelDesc* desc, const float* const* params, 
         hipLaunchKernelGGL(nsff_pack_kernel_h3, dim3((max_threads + 255) / 256, n), dim3(256), 0, st, pa);
     }
     return fold ? nsff_h3_fold_heads(desc, params, packed, st) : nsff_launch_status();
+}
+
+// The packed buffer of nsff_field_kernel_h3a16: the same NsffLayoutH3, the same values; the trunk segments (seg_x, seg_h of either
+// trunk) hold their 16-byte chunks in the order of the v_mfma_f32_16x16x32_f16 A operand (tools/h3asm/gen.py, SHAPE): chunk
+// [wave][slot j][mt'][part][lane = 16 g + c] = part(W[64 wave + 16 (2 (j & 1) + mt') + c][col(32 (j >> 1) + 8 g + t)]), which the
+// 32-shape pack keeps at [wave][ks = (j & ~1) + (g >> 1)][mt = j & 1][part][lane = 32 (g & 1) + 16 mt' + c].  Everything else is copied.
+constexpr int REPACK_BATCH = 64;
+struct RepackArgsH3 { const u4v* src; u4v* dst; uint32_t off[REPACK_BATCH]; int32_t nks[REPACK_BATCH]; };
+__global__ __launch_bounds__(256) void nsff_repack_kernel_h3a16(const RepackArgsH3 a) {
+    const int nks = a.nks[blockIdx.y];
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 4 * nks * 4 * 64) return;              // chunks: [wave][slot][mt'][part][lane]
+    const int lane = idx & 63, part = (idx >> 6) & 1, mt = (idx >> 7) & 1, wk = idx >> 8;
+    const int j = wk % nks, wave = wk / nks, g = lane >> 4, c = lane & 15;
+    const int src = ((((wave * nks + (j & ~1) + (g >> 1)) * 2 + (j & 1)) * 2 + part) << 6) + 32 * (g & 1) + 16 * mt + c;
+    const size_t base = a.off[blockIdx.y] / 4;        // (segment offsets are multiples of four words)
+    a.dst[base + idx] = a.src[base + src];
+}
+
+int nsff_h3_repack_weights(const NsffModelDesc* desc, const void* packed, void* repacked, hipStream_t st) {
+    NsffLayoutH3 L;
+    const int rc = nsff_make_layout_h3(*desc, L);
+    if (rc) return rc;
+    // (the permutation reads the first pack while it writes the second: the two may not overlap)
+    const char* const p0 = reinterpret_cast<const char*>(packed);
+    const char* const r0 = reinterpret_cast<const char*>(repacked);
+    if (p0 < r0 + (size_t)L.total * 4 && r0 < p0 + (size_t)L.total * 4) return NSFF_ERR_INVALID;
+    hipError_t e = hipMemcpyAsync(repacked, packed, (size_t)L.total * 4, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return nsff_hip_fail(e);
+    RepackArgsH3 ra{};
+    ra.src = reinterpret_cast<const u4v*>(packed);
+    ra.dst = reinterpret_cast<u4v*>(repacked);
+    int n = 0;
+    bool bad = false;
+    constexpr int REPACK_MAX_NKS = NSFF_W / 16;      // grid.x below covers the 1024 nks chunks of a segment of at most 256 columns
+    auto flush = [&]() {
+        if (n > 0) hipLaunchKernelGGL(nsff_repack_kernel_h3a16, dim3(4 * REPACK_MAX_NKS, n), dim3(256), 0, st, ra);
+        n = 0;
+    };
+    auto trunk = [&](const NsffTrunkLayoutH3& T) {
+        for (int l = 0; l < desc->D; ++l) {
+            const uint32_t off[2] = {T.seg_x[l], T.seg_h[l]};
+            const int nks[2] = {(int)T.k0 / 16, NSFF_W / 16};
+            for (int i = 0; i < 2; ++i) {
+                if (off[i] == NSFF_NONE) continue;
+                if (nks[i] > REPACK_MAX_NKS || (nks[i] & 1)) { bad = true; continue; }      // (wider than the grid; a step pairs two k-steps)
+                ra.off[n] = off[i]; ra.nks[n] = nks[i];
+                if (++n == REPACK_BATCH) flush();
+            }
+        }
+    };
+    trunk(L.st);
+    if (desc->has_transient) trunk(L.tr);
+    flush();
+    return bad ? NSFF_ERR_INVALID : nsff_launch_status();
 }
 
 // Folded head rows (NsffLayoutH3): products in fp32 scratch inside the packed buffer, then one head tile per trunk.
@@ -2302,6 +2377,7 @@ static int h3a_device_cus() {
     return cus[dev] > 0 ? cus[dev] : 0;
 }
 
+int g_nsff_last_h3_shape = 0;         // MFMA shape of the trunk phases of the last f16x3 launch (nsff_last_field_mfma_shape): 32 | 16
 int g_nsff_last_h3_grid = 0;          // workgroups of that launch when it was a hand-scheduled inference launch (nsff_last_field_grid)
 
 // The [dir | a] input tile of static_dir_encoding as the weight-gradient GEMM of those columns reads it (NsffFieldArgs::save_side:
@@ -2389,6 +2465,8 @@ struct H3Launch { int kernel; unsigned grid, block; };       // kernel: NSFF_LAU
 struct H3Plan {
     int kernel;            // NSFF_KERNEL_* that nsff_last_field_kernel reports (0: none decided)
     int grid;              // what nsff_last_field_grid reports
+    int shape;             // MFMA shape of the trunk phases: 16 = the NSFF_LAUNCH_H3A launch is nsff_field_kernel_h3a16 (same arguments, the
+                           // repacked buffer); 32 everywhere else
     int n;
     H3Launch launch[3];
     SideTileArgs side;     // of NSFF_LAUNCH_SIDE_TILE
@@ -2468,8 +2546,23 @@ static unsigned h3a_plan_persistent(H3AArgs& ka, long long tiles, int n_cus, boo
 // points_per_block 64: the 64-point tiling.  130 / 131: 128 points per workgroup -- the hand-scheduled body (nsff_field_kernel_h3a,
 // training forward: nsff_field_kernel_h3a_save) whenever it covers the launch, otherwise -- and always with 131 -- eight waves of
 // 32 neurons, compiler-scheduled (half the weight stream of the 64-point tiling).
+// shape_req: the shape asked for (h3a_shape_for) -- the 16-shape body runs the inference launches
+// whose phase programs hold no sigma ride (no A16RS / B16RS phase, i.e. not the side-fold program) and whose static trunk is not
+// the eight-wave kernel's beside it: h3a / h3a_tb in the per-tile and both persistent forms.  The choice depends on the model and
+// the request alone -- never on the launch's size, its form or its chunking -- so two launches of one model that a test compares bit
+// for bit (persistent / per-tile, merged / split re-query, chunked / whole frame, graph / eager) that both run the hand-scheduled
+// kernel run the same shape.
+// Default 16 where the caller handed over the repacked buffer (measured on the C2 headline, EXPERIMENTS.md section R11: 1.895 -> 1.792 ms
+// per step); a caller without one (plain nsff_field_query) keeps 32.  NSFF_H3A_SHAPE=32 | 16 of the environment forces either.
+constexpr int H3A_DEFAULT_SHAPE = 16;
+static int h3a_shape_for(bool has_repacked) {
+    const char* e = getenv("NSFF_H3A_SHAPE");          // (read per launch: tests flip it)
+    const int req = e == nullptr ? 0 : (atoi(e) == 16 ? 16 : (atoi(e) == 32 ? 32 : 0));
+    return req ? req : (has_repacked ? H3A_DEFAULT_SHAPE : 32);
+}
 static int h3_plan_launch(const NsffModelDesc& d, const H3KArgs& k, const NsffFieldArgs& g, int points_per_block, int n_cus,
-                          bool no_persist, H3Plan& p) {
+                          bool no_persist, int shape_req, H3Plan& p) {
+    p.shape = 32;
     const bool saves = k.save_acts || k.save_xin || k.save_masks || k.save_side;      // training forward
     // one trunk per workgroup when the launch evaluates both (see the kernel): grid = 2 x tiles
     const bool both = k.n_steps > k.n_static_steps && k.n_static_steps > 0;
@@ -2567,21 +2660,30 @@ static int h3_plan_launch(const NsffModelDesc& d, const H3KArgs& k, const NsffFi
         grid = h3a_plan_persistent(ka, tiles, n_cus, no_persist, both ? 2 : 1);
     }
     p.launch[p.n++] = H3Launch{NSFF_LAUNCH_H3A, grid, 256};
+    if (!side && !two_launches && !d.use_viewdir) p.shape = shape_req == 16 ? 16 : 32;
     p.kernel = side ? NSFF_KERNEL_H3A_SIDE : (ka.k.t_bias ? NSFF_KERNEL_H3A_TBIAS : NSFF_KERNEL_H3A);
     p.grid = (int)grid;
     return NSFF_OK;
 }
 
 int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const NsffFieldArgs* args,
-                        int points_per_block, hipStream_t st, unsigned long long* span) {
+                        int points_per_block, hipStream_t st, unsigned long long* span, const void* repacked) {
     H3KArgs k{};
     H3Plan p{};
     int rc = h3_fill_args(*desc, *args, packed, span, nsff_range_word(st), k);
     // NSFF_NO_PERSIST=1: one workgroup per tile (A/B; the variable is read per launch: tests flip it)
-    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k, *args, points_per_block, h3a_device_cus(), getenv("NSFF_NO_PERSIST") != nullptr, p);
+    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k, *args, points_per_block, h3a_device_cus(), getenv("NSFF_NO_PERSIST") != nullptr,
+                                           h3a_shape_for(repacked != nullptr), p);
     g_nsff_last_h3_grid = p.grid;
     if (p.kernel) g_nsff_last_h3_kernel = p.kernel;
     if (rc != NSFF_OK) return rc;
+    // the 16-shape kernel reads the repacked buffer (nsff_repack_field_weights): a launch planned for it without one is an error
+    if (p.shape == 16) {
+        if (repacked == nullptr) return NSFF_ERR_NULL;
+        if ((uintptr_t)repacked & 15) return NSFF_ERR_ALIGN;
+        p.ka.k.packed = reinterpret_cast<const uint32_t*>(repacked);
+    }
+    if (p.kernel) g_nsff_last_h3_shape = p.shape;       // (behind the last refusal: the shape of launches that are issued)
     for (int i = 0; i < p.n; ++i) {
         const dim3 grid(p.launch[i].grid), block(p.launch[i].block);
         switch (p.launch[i].kernel) {              // (the templates in the order they have always been instantiated: same device binary)
@@ -2590,7 +2692,10 @@ int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const Nsf
         case NSFF_LAUNCH_H3_8WAVE_SAVE: hipLaunchKernelGGL((nsff_field_kernel_h3<4, 1, true, 1>), grid, block, 0, st, p.k); break;
         case NSFF_LAUNCH_H3_64:         hipLaunchKernelGGL((nsff_field_kernel_h3<2, 1>), grid, block, 0, st, p.k); break;
         case NSFF_LAUNCH_H3_8WAVE:      hipLaunchKernelGGL((nsff_field_kernel_h3<4, 1, false, 1>), grid, block, 0, st, p.k); break;
-        case NSFF_LAUNCH_H3A:           hipLaunchKernelGGL(nsff_field_kernel_h3a, grid, block, 0, st, p.ka); break;
+        case NSFF_LAUNCH_H3A:
+            if (p.shape == 16) hipLaunchKernelGGL(nsff_field_kernel_h3a16, grid, block, 0, st, p.ka);
+            else hipLaunchKernelGGL(nsff_field_kernel_h3a, grid, block, 0, st, p.ka);
+            break;
         case NSFF_LAUNCH_H3A_SAVE:      hipLaunchKernelGGL(nsff_field_kernel_h3a_save, grid, block, 0, st, p.ka); break;
         }
     }
@@ -2615,7 +2720,7 @@ extern "C" int nsff_field_launch_plan(const NsffModelDesc* desc, const NsffField
     H3KArgs k{};
     H3Plan p{};
     int rc = h3_fill_args(*desc, *args, nullptr, nullptr, nullptr, k);
-    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k, *args, tp ? tp : nsff_h3_default_tile(args->n_points), n_cus, no_persist != 0, p);
+    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k, *args, tp ? tp : nsff_h3_default_tile(args->n_points), n_cus, no_persist != 0, 32, p);
     if (rc != NSFF_OK) return rc;
     for (int i = 0; i < p.n; ++i) {
         int32_t* o = out + i * NSFF_PLAN_WORDS;
@@ -2629,6 +2734,18 @@ extern "C" int nsff_field_launch_plan(const NsffModelDesc* desc, const NsffField
         o[11] = (int32_t)(a ? nsff_plan_hash(&p.ka, sizeof p.ka) : nsff_plan_hash(&p.k, sizeof p.k));
     }
     return p.kernel;
+}
+
+// Host-only: the MFMA shape nsff_field_query_repacked would run these arguments' trunk phases on under the current environment (32
+// for every launch that is not the hand-scheduled inference kernel's) -- a caller asks before it builds the repacked buffer.
+int nsff_h3_field_mfma_shape(const NsffModelDesc* desc, const NsffFieldArgs* args) {
+    const int tp = args->tile_points;
+    if (tp != 0 && tp != 64 && tp != 130 && tp != 131) return NSFF_ERR_INVALID;
+    H3KArgs k{};
+    H3Plan p{};
+    int rc = h3_fill_args(*desc, *args, nullptr, nullptr, nullptr, k);
+    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k, *args, tp ? tp : nsff_h3_default_tile(args->n_points), 0, true, h3a_shape_for(true), p);
+    return rc != NSFF_OK ? rc : p.shape;
 }
 
 // Host-only export of what a launch would execute (no GPU work): the step program and, when the hand-scheduled body covers the
@@ -2656,7 +2773,7 @@ extern "C" int nsff_field_phase_program(const NsffModelDesc* desc, int static_mo
     H3KArgs k0{};
     H3Plan p{};
     int rc = h3_fill_args(*desc, g, nullptr, nullptr, nullptr, k0);
-    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k0, g, 130, 0, true, p);
+    if (rc == NSFF_OK) rc = h3_plan_launch(*desc, k0, g, 130, 0, true, 32, p);
     if (rc) return rc;
     const bool body = p.launch[p.n - 1].kernel == NSFF_LAUNCH_H3A;
     const H3KArgs& k = body ? p.ka.k : p.k;

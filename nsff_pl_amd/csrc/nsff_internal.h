@@ -14,7 +14,12 @@ int nsff_fold_rows_f32(const NsffModelDesc* desc, const float* const* params, fl
 // workgroups in shader-clock ticks [0] and in wall-clock ticks [1]
 #define NSFF_SPAN_WORDS 2
 int nsff_h3_field_query(const NsffModelDesc* desc, const void* packed, const NsffFieldArgs* args,
-                        int points_per_block, hipStream_t st, unsigned long long* span = nullptr);
+                        int points_per_block, hipStream_t st, unsigned long long* span = nullptr, const void* repacked = nullptr);
+// the 16x16x32 form of the hand-scheduled inference kernel (nsff_field_kernel_h3a16): its packed buffer from the f16x3 pack, the shape
+// a launch would run (host-only), the shape the last f16x3 launch ran
+int nsff_h3_repack_weights(const NsffModelDesc* desc, const void* packed, void* repacked, hipStream_t st);
+int nsff_h3_field_mfma_shape(const NsffModelDesc* desc, const NsffFieldArgs* args);
+extern int g_nsff_last_h3_shape;
 
 // the library's choice of points_per_block (NsffFieldArgs::tile_points = 0): 128 points as eight waves of 32 neurons (one
 // workgroup per CU, every weight byte fetched once per 128 points, no spilled registers: 41 MB instead of 79 MB of HBM traffic

@@ -20,7 +20,8 @@ subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-
                       stderr=subprocess.DEVNULL)
 txt = open(out).read()
 failed = []
-for kernel in ("nsff_field_kernel_h3a", "nsff_field_kernel_h3a_save"):          # inference body, training-forward (SAVE) body
+# inference body, training-forward (SAVE) body, the inference body on 16x16x32 MFMAs
+for kernel in ("nsff_field_kernel_h3a", "nsff_field_kernel_h3a_save", "nsff_field_kernel_h3a16"):
   m = re.search(r'^(_ZN\S*' + kernel + r'E\S*):', txt, re.M)
   name = m.group(1)
   body = txt[m.end():]

@@ -40,14 +40,26 @@ def split_rtz(x):
     return hi.astype(np.float16), lo.astype(np.float16)
 
 
-def pack_segment(W):
-    """W (256, K) fp32, K = 16 nks -> u32 stream [wave][ks][mt][part][lane][8 halfs], hi = fp16(x) to nearest, lo = fp16(x - hi)"""
+def pack_segment(W, shape=32):
+    """W (256, K) fp32, K = 16 nks -> u32 stream [wave][ks][mt][part][lane][8 halfs], hi = fp16(x) to nearest, lo = fp16(x - hi)
+    shape 16 (gen.SHAPE): the same values in the order of the 16x16x32 operand -- slot j = 2 s + (mi >> 1), chunk mt' = mi & 1, lane =
+    (g, c): neuron 64 wave + 16 mi + c, column 32 s + 8 g + t"""
     K = W.shape[1]
     nks = K // 16
     hi = W.astype(np.float16)
     lo = (W - hi.astype(np.float32)).astype(np.float16)
     out = np.zeros((4, nks, 2, 2, 64, 8), np.float16)
     lane = np.arange(64)
+    if shape == 16:
+        for wv in range(4):
+            for j in range(nks):
+                for mt in range(2):
+                    n = 64 * wv + 16 * (2 * (j & 1) + mt) + (lane & 15)
+                    for t in range(8):
+                        c = 32 * (j >> 1) + 8 * (lane >> 4) + t
+                        out[wv, j, mt, 0, :, t] = hi[n, c]
+                        out[wv, j, mt, 1, :, t] = lo[n, c]
+        return out.reshape(-1).view(np.uint32), hi, lo
     for wv in range(4):
         for ks in range(nks):
             for mt in range(2):
@@ -156,7 +168,7 @@ def build_program(segs, in_t, head=None, sig_row=None, save=False, persist=False
     return ph
 
 
-def make_case(kind, seed=0):
+def make_case(kind, seed=0, shape=32):
     rng = np.random.RandomState(seed)
     # *_tb: the dynamic trunk with the time code folded into per-ray bias rows (every 64-point half inside one ray): the body runs
     # the position part of the input segments only (4 of their 8 k-steps), the table holds b + W_t t(ray of the half)
@@ -173,7 +185,7 @@ def make_case(kind, seed=0):
 
     def add_seg(W, bias, post, rebuild):
         nonlocal off
-        stream, hi, lo = pack_segment(W)
+        stream, hi, lo = pack_segment(W, shape)
         bidx = None
         if bias is not None:
             bidx = len([s_ for s_ in segs if s_["bias"] is not None])
@@ -289,16 +301,17 @@ def head_reference(case, xh_, xl_):
     return ((c[0] + c[1]).astype(np.float32) + c[2]).astype(np.float32)[:, :hd["n_rows"]]
 
 
-def run_case(kind, seed=0, verbose=True, poke=None):
-    """poke (or None): a value put into neuron 5 of layer 0's bias row -- the tile's activations of that neuron leave the fp16
+def run_case(kind, seed=0, verbose=True, poke=None, shape=32):
+    """shape: the MFMA shape of the trunk phases (gen.SHAPE; 16: the body of nsff_field_kernel_h3a16 on weights packed in its order)
+    poke (or None): a value put into neuron 5 of layer 0's bias row -- the tile's activations of that neuron leave the fp16
     range when it is large; the run then returns the value-domain word the body left instead of checking the arithmetic."""
     save = kind.endswith("_save")
     persist = kind.endswith("_persist")
-    case = make_case(kind[:-5] if save else (kind[:-8] if persist else kind), seed)
+    case = make_case(kind[:-5] if save else (kind[:-8] if persist else kind), seed, shape)
     if poke is not None:
         case["rows"][0] = case["rows"][0].copy()
         case["rows"][0][5] = np.float32(poke)
-    pre, prog, _ = gen.build(save=save)
+    pre, prog, _ = gen.build(save=save, shape=shape)
     sim = Sim(pre + prog)                      # the two asm statements back to back (the encoder between them is C++)
     sim.add_buffer(PK_BASE, case["pk"])
     body_in_t = 0 if case["tb"] else case["in_t"]       # (the body sees no time-code columns when they are folded into the table)
@@ -432,7 +445,7 @@ def run_case(kind, seed=0, verbose=True, poke=None):
                         want_w = case["pk"][(base + 1024 * c + 16 * lane) // 4 + e_]
                         assert np.array_equal(w.a[16 * k + 4 * c + e_], want_w), (w.id, k, c, e_)
     n_mf = sim.waves[0].n_mfma
-    want_mf = sum(sg["nks"] for sg in case["segs"]) * 24 + 48
+    want_mf = sum(sg["nks"] for sg in case["segs"]) * (48 if shape == 16 else 24) + 48
     if verbose:
         print(f"{kind:9s} phases {len(phases) - 2:2d}  MFMAs/wave {n_mf} (expected {want_mf})  instructions/wave {sim.waves[0].n_inst}  "
               f"max-norm rel err {err:.2e}  |want| max {np.abs(want).max():.3g}  ({dt:.1f} s)")
@@ -441,7 +454,19 @@ def run_case(kind, seed=0, verbose=True, poke=None):
     return err
 
 
+# the programs the 16-shape body covers: everything of the inference list but the view-direction trunks (the sigma ride is 32-shape only)
+KINDS16 = ["static", "dynamic", "noskip", "twoskips", "dynamic_tb", "twoskips_tb", "static_persist", "dynamic_tb_persist"]
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--shape16"]:
+        for k in sys.argv[2:] or KINDS16:
+            try:
+                run_case(k, shape=16)
+            except SimError as e:
+                sys.exit(f"{k} (16-shape): SIMULATION ERROR: {e}")
+        print("simulation OK (16-shape)")
+        sys.exit(0)
     kinds = sys.argv[1:] or ["static", "dynamic", "noskip", "twoskips", "dynamic_tb", "twoskips_tb", "viewdir",
                              "static_save", "dynamic_save", "twoskips_save", "viewdir_save", "static_persist", "dynamic_tb_persist",
                              "viewdir_persist"]

@@ -110,6 +110,21 @@ def I_v_fmac(d, a, b):
     return Inst("v_fmac_f32", f"v_fmac_f32_e32 {d}, {a}, {b}", [a, b, d], [d], "valu", dict(d=d, s=[a, b, d]))
 
 
+# ---- the MFMA shape of the trunk phases (build(shape=...)): 32 = v_mfma_f32_32x32x16_f16 (everything above), 16 =
+# v_mfma_f32_16x16x32_f16 over the SAME schedule (inference build only -> field_h3a16_body.inc).  With g = lane >> 4, c = lane & 15:
+#   * acc(half, mi, ni), mi, ni = 0..3: four registers, register e = neuron 64 wave + 16 mi + 4 g + e at point 16 ni + c of the half;
+#   * an S16 step s covers K = 32 = the old k-steps 2 s, 2 s + 1; its weights a[32 s + 8 mi + 4 part : +4] are the ring's slots 2 s
+#     (mi 0, 1) and 2 s + 1 (mi 2, 3): half t of a lane = part(W[64 wave + 16 mi + c][col(32 s + 8 g + t)]) -- the values of the
+#     32-shape pack in another order (nsff_repack_kernel_h3a16); slots, streams, descriptors and phase programs are unchanged;
+#   * it runs as two HALF-STEPS q = 0, 1 over the point pairs ni = 2 q, 2 q + 1, which take the place of the old k-steps 2 s + q:
+#     the same 2 + 2 fragment reads into the same registers (row 16 ni + c at byte 64 s + 16 g), 24 MFMAs of 4 passes for 12 of 8;
+#   * both slots of a step are free only behind half-step (s, 1): slot j is refilled beside half-step j + 2 (32-shape: j + 1).
+# The HEAD phase keeps the 32x32x16 tile (its input is the LDS tile) and computes its own read addresses; the sigma ride and the SAVE
+# build have no 16-shape form.
+SHAPE = 32
+RIDE_CAP16 = int(os.environ.get("H3A_RIDE_CAP16", "3"))   # short B phases, 16-shape: twice the gaps, each half as long, 8 of 16 cycles held
+
+
 def xh(b, nt):
     return V(XH0 + 8 * b + 4 * nt, 4)
 
@@ -119,10 +134,14 @@ def xl(nt):
 
 
 def acc(half, mt, nt):
+    if SHAPE == 16:
+        return V(ACC[half] + 4 * (4 * mt + nt), 4)
     return V(ACC[half] + 16 * (2 * mt + nt), 16)
 
 
-def wslot(ks, mt, part):     # part 0 = hi, 1 = lo
+def wslot(ks, mt, part):     # part 0 = hi, 1 = lo  (16-shape: ks = the step s, mt = mi)
+    if SHAPE == 16:
+        return A(32 * ks + 8 * mt + 4 * part, 4)
     return A(16 * ks + 8 * mt + 4 * part, 4)
 
 
@@ -210,6 +229,8 @@ def epilogue_unit(half, u, tset, sig=False):
     """ReLU -> hi / lo split -> four 8-byte LDS stores (two per plane) of (tile u>>1, quad pair p = u&1) of `half`'s accumulators.
     In place on the accumulator registers; 8 temporaries from set `tset`.  (Until late in round 4: lanes i, i+32 traded halves with
     v_permlane32_swap for two 16-byte stores -- two instructions more per unit, +0.6 % on the C2 step.)"""
+    if SHAPE == 16:
+        return epilogue_unit16(half, u, tset)
     t, p = u >> 1, u & 1
     mt, nt = t >> 1, t & 1
     a = acc(half, mt, nt)
@@ -253,6 +274,26 @@ def epilogue_unit(half, u, tset, sig=False):
     if SAVE and u in (3, 7):   # word mt complete: lane's 4 bytes at S_MASK + 8 (lane) + 4 mt (+ 2 KiB: the tile of half B)
         out += [I_valu("v_lshrrev_b32", V_TMP, 1, V_LANE16),
                 _nt(I_gstore_s(V_TMP, V_MSKW, S_MASK, 4 * mt + (2048 if half == "B" else 0)))]
+    return range_check_unit(out, x, H, u)
+
+
+def epilogue_unit16(half, u, tset):
+    """16-shape: the unit covers the tiles (mi = u >> 1, ni = 2 (u & 1) + j), j = 0, 1 -- the four registers of a tile are four
+    consecutive neurons at one point: the same conversion sequence, then one 8-byte store per tile and plane (write base
+    c LDH_B + 8 g + 128 wave, immediate 16 LDH_B ni + 32 mi)."""
+    assert not SAVE
+    mi, ni0 = u >> 1, 2 * (u & 1)
+    x = [acc(half, mi, ni0 + j).sub(e) for j in range(2) for e in range(4)]
+    H = [V(T0 + 8 * tset + k) for k in range(4)]
+    L = [V(T0 + 8 * tset + 4 + k) for k in range(4)]
+    out = [I_v_max0(r, r) for r in x]
+    out += [I_v_cvt_pkrtz(H[k], x[2 * k], x[2 * k + 1]) for k in range(4)]
+    for k in range(4):
+        out += [I_v_sub_lo_half(x[2 * k], H[k], x[2 * k]), I_v_sub_hi_half(x[2 * k + 1], H[k], x[2 * k + 1])]
+    out += [I_v_cvt_pkrtz(L[k], x[2 * k], x[2 * k + 1]) for k in range(4)]
+    off = [half_off(half) + 16 * LDH_B * (ni0 + j) + 32 * mi for j in range(2)]
+    out += [I_ds_write_b64(V_WR_H, V(H[0].i, 2), off[0]), I_ds_write_b64(V_WR_H, V(H[2].i, 2), off[1]),
+            I_ds_write_b64(V_WR_L, V(L[0].i, 2), off[0]), I_ds_write_b64(V_WR_L, V(L[2].i, 2), off[1])]
     return range_check_unit(out, x, H, u)
 
 
@@ -352,6 +393,8 @@ def sigma_weight_reads():
 def init_reads(half):
     """acc_<half> := bias of the segment whose table offset is in V_BADDR (16 x ds_read_b128 straight into the accumulators)"""
     out = []
+    if SHAPE == 16:         # (bias base + 16 g: neurons 16 mi + 4 g .. + 3, the same read for the four ni)
+        return [I_ds_read_b128(acc(half, mi, ni), V_BADDR, 64 * mi) for mi in range(4) for ni in range(4)]
     for mt in range(2):
         for nt in range(2):
             for q in range(4):
@@ -359,7 +402,14 @@ def init_reads(half):
     return out
 
 
+def frag_off16(half, ks, j):
+    """16-shape: half-step ks = (s, q) = (ks >> 1, ks & 1) reads the fragments of ni = 2 q + j: row 16 ni + c at byte 64 s + 16 g"""
+    return half_off(half) + 16 * LDH_B * (2 * (ks & 1) + j) + 64 * (ks >> 1)
+
+
 def frag_reads_h(half, ks, b):
+    if SHAPE == 16:
+        return [I_ds_read_b128(xh(b, j), V_RD_H, frag_off16(half, ks, j)) for j in range(2)]
     return [I_ds_read_b128(xh(b, nt), V_RD_H, half_off(half) + NT_B * nt + 32 * ks) for nt in range(2)]
 
 
@@ -368,12 +418,22 @@ def xl2(nt):
 
 
 def frag_reads_l(half, ks, second=False):
+    if SHAPE == 16:
+        return [I_ds_read_b128(xl2(j) if second else xl(j), V_RD_L, frag_off16(half, ks, j)) for j in range(2)]
     return [I_ds_read_b128(xl2(nt) if second else xl(nt), V_RD_L, half_off(half) + NT_B * nt + 32 * ks) for nt in range(2)]
 
 
 def mfmas(half, ks, second_xl=False):
     b = ks & 1
     out = []
+    if SHAPE == 16:         # half-step (s, q) = (ks >> 1, ks & 1): three parts x four mi x the two ni = 2 q + j
+        for part, xsel in ((1, "h"), (0, "h"), (0, "l")):
+            for mi in range(4):
+                for j in range(2):
+                    d = acc(half, mi, 2 * b + j)
+                    bop = xh(b, j) if xsel == "h" else (xl2(j) if second_xl else xl(j))
+                    out.append(I_mfma16(d, wslot(ks >> 1, mi, part), bop, d))
+        return out
     for part, xsel in ((1, "h"), (0, "h"), (0, "l")):      # Wl.xh, Wh.xh, Wh.xl: the lo fragments are needed last
         for mt in range(2):
             for nt in range(2):
@@ -515,7 +575,11 @@ def phase_body(name, half, nks, ride=None, refills=False, tail_init=False, rebui
     s.emit(I_label(f"L_{name}"))
     oh = other(half)
     last = nks - 1
-    bar = (last - 1, 8)
+    # MFMAs per k-step (16-shape: per half-step), the first one that reads the lo fragments, and how many k-steps behind its last use a
+    # weight slot is refilled, in the gaps refill_gap[piece]
+    nm, m_xl, lag = (24, 16, 2) if SHAPE == 16 else (12, 8, 1)
+    refill_gap = {(2 * g if SHAPE == 16 else g): g - 3 for g in range(3, 8)}
+    bar = (last - 1, m_xl)
     for nt in range(2):
         s.lds_q.append((("xh", 0), None))
     for nt in range(2):
@@ -537,7 +601,7 @@ def phase_body(name, half, nks, ride=None, refills=False, tail_init=False, rebui
     if copy:                # (SAVE) this half's input tile goes to HBM while the phase multiplies it
         ride_ins = merge_ride(ride_ins, copy_groups(half))
     rb_parts = rebuild_parts(rebuild, name) if rebuild is not None else None
-    ride_gaps = [(ks, m) for ks in range(1, nks) for m in range(12) if (ks, m) < (bar[0], bar[1] - 1)]
+    ride_gaps = [(ks, m) for ks in range(1, nks) for m in range(nm) if (ks, m) < (bar[0], bar[1] - 1)]
     per_gap = dict(zip(ride_gaps, spread(len(ride_ins), len(ride_gaps)))) if ride_ins else {}
     pieces = []
     if stream_slots is not None:
@@ -547,7 +611,7 @@ def phase_body(name, half, nks, ride=None, refills=False, tail_init=False, rebui
         s.emit(I_salu("s_add_u32", S_R2, S_R2, 4096 * stream_slots[0], scc=True))
         for slot in stream_slots:
             pieces += [(slot, pc) for pc in refill(slot)]
-        every = max(1, (12 * nks - 2) // len(pieces))
+        every = max(1, (nm * nks - 2) // len(pieces))
     if refills and one_stream:
         s.emit(refill_start(S_R1))
     ri = pi = gi = 0
@@ -556,12 +620,15 @@ def phase_body(name, half, nks, ride=None, refills=False, tail_init=False, rebui
             # ---- in front of the MFMA
             if m == 0:
                 if vm_mode == "formula":
-                    # (+ the stores this phase has issued so far: they are younger entries of the same in-order queue)
-                    s.wait(vm=min(4 * (15 - ks) + sum(1 for i_ in s.ins if i_.op == "gstore_s"), 63))
+                    # (+ the stores this phase has issued so far: they are younger entries of the same in-order queue;
+                    #  16-shape: a step reads slots 2 s and 2 s + 1)
+                    s.wait(vm=min(4 * (15 - (ks | 1 if SHAPE == 16 else ks)) + sum(1 for i_ in s.ins if i_.op == "gstore_s"), 63))
                 elif vm_mode == "model":
                     s.need_vm(("w", ks))
+                    if SHAPE == 16:
+                        s.need_vm(("w", ks | 1))
                 s.need_lds(("xh", ks))
-            if m == 8:
+            if m == m_xl:
                 s.need_lds(("xl", ks))
             if (ks, m) == bar:
                 stamp(2)
@@ -578,14 +645,14 @@ def phase_body(name, half, nks, ride=None, refills=False, tail_init=False, rebui
                 if ks + 1 == last:                      # the last k-step's lo fragments: second buffer, requested a k-step early
                     for r in frag_reads_l(half, last, second=True):
                         s.emit(r, ("xl", last))
-            if m == 11 and ks + 1 < last:
+            if m == nm - 1 and ks + 1 < last:
                 for r in frag_reads_l(half, ks + 1):
                     s.emit(r, ("xl", ks + 1))
             if rebuild is not None and m == 2 and ks in (0, max(1, (nks - 1) // 2)):
                 emit_rebuild(s, rb_parts[0 if ks == 0 else 1], ks == 0)
-            if refills and ks >= 1 and 3 <= m <= 7 and (refill_slots is None or ks - 1 in refill_slots):
-                for r in refill(ks - 1, one_stream)[m - 3]:
-                    s.emit(r, ("w", ks - 1))
+            if refills and ks >= lag and m in refill_gap and (refill_slots is None or ks - lag in refill_slots):
+                for r in refill(ks - lag, one_stream)[refill_gap[m]]:
+                    s.emit(r, ("w", ks - lag))
             if pieces and gi % every == 0 and pi < len(pieces):
                 for r in pieces[pi][1]:
                     s.emit(r, ("w", pieces[pi][0]))
@@ -602,9 +669,11 @@ def phase_body(name, half, nks, ride=None, refills=False, tail_init=False, rebui
             if ks == last and m == 0:
                 for r in frag_reads_l(oh, 0):
                     s.emit(r, ("xl'", 0))
-            if ks == last and m == 11 and refills and (refill_slots is None or last in refill_slots):
-                for r in refill_flat(last, one_stream):
-                    s.emit(r, ("w", last))
+            if ks == last and m == nm - 1 and refills:
+                for slot in range(last - lag + 1, last + 1):
+                    if refill_slots is None or slot in refill_slots:
+                        for r in refill_flat(slot, one_stream):
+                            s.emit(r, ("w", slot))
     assert ri == len(ride_ins) and pi == len(pieces)
     stamp(4)
     s.emit(I_branch("s_branch", "L_dispatch"))
@@ -631,11 +700,13 @@ def short_b_body(name, nks):
     s.emit(refill_start(S_R1))          # (a 16-k-step segment follows a short one: one refill stream)
     ride_ins = epilogue_stream("A")
     ri = 0
+    nm, m_xl, lag, cap = (24, 16, 2, RIDE_CAP16) if SHAPE == 16 else (12, 8, 1, RIDE_CAP)
+    refill_gap = {(2 * g if SHAPE == 16 else g): g - 3 for g in range(3, 8)}
     for ks in range(nks):
         for m, mf in enumerate(mfmas("B", ks)):
             if m == 0:
                 s.need_lds(("xh", ks))
-            if m == 8:
+            if m == m_xl:
                 s.need_lds(("xl", ks))
             if ks == 0 and m == 0:
                 stamp(1)
@@ -643,19 +714,20 @@ def short_b_body(name, nks):
             if m == 0 and ks < last:
                 for r in frag_reads_h("B", ks + 1, (ks + 1) & 1):
                     s.emit(r, ("xh", ks + 1))
-            if m == 11 and ks < last:
+            if m == nm - 1 and ks < last:
                 for r in frag_reads_l("B", ks + 1):
                     s.emit(r, ("xl", ks + 1))
-            if ks >= 1 and 3 <= m <= 7:
-                for r in refill(ks - 1, True)[m - 3]:
-                    s.emit(r, ("w", ks - 1))
+            if ks >= lag and m in refill_gap:
+                for r in refill(ks - lag, True)[refill_gap[m]]:
+                    s.emit(r, ("w", ks - lag))
             if ks >= 1:
-                for _ in range(RIDE_CAP if not (3 <= m <= 7) else RIDE_CAP - 1):
+                for _ in range(cap if not (ks >= lag and m in refill_gap) else cap - 1):
                     if ri < len(ride_ins):
                         emit_ride(s, ride_ins[ri])
                         ri += 1
-    for r in refill_flat(last, True):
-        s.emit(r, ("w", last))
+    for slot in range(last - lag + 1, last + 1):
+        for r in refill_flat(slot, True):
+            s.emit(r, ("w", slot))
     stamp(2)
     while ri < len(ride_ins):
         emit_ride(s, ride_ins[ri])
@@ -704,8 +776,17 @@ def head_body():
     e(I_label("L_HEAD"))
     vbh, vbl, vw, v4h, t0 = V(T0), V(T0 + 1), V(T0 + 2), V(T0 + 3), V(T0 + 4)
     e(I_salu("s_mul_i32", S_T0, S_WAVE, NT_B))
-    e(I_valu("v_add_u32", vbh, S_T0, V_RD_H, text=f"v_add_u32_e32 {vbh}, {S_T0}, {V_RD_H}"))
-    e(I_valu("v_add_u32", vbl, S_T0, V_RD_L, text=f"v_add_u32_e32 {vbl}, {S_T0}, {V_RD_L}"))
+    if SHAPE == 16:
+        # (the trunk's read bases are the 16-shape's: this phase's 32x32x16 fragments -- row lane & 31 at byte 16 (lane >> 5) -- get their own)
+        e(I_valu("v_lshrrev_b32", t0, 4, V_LANE16)); e(I_valu("v_and_b32", v4h, 31, t0))
+        e(I_valu("v_mul_u32_u24", vbh, LDH_B, v4h))
+        e(I_valu("v_lshrrev_b32", t0, 5, t0)); e(I_valu("v_lshlrev_b32", t0, 4, t0)); e(I_valu("v_add_u32", vbh, vbh, t0))
+        e(I_salu("s_add_u32", S_T0, S_T0, S_LDS, scc=True))
+        e(I_valu("v_add_u32", vbh, S_T0, vbh, text=f"v_add_u32_e32 {vbh}, {S_T0}, {vbh}"))
+        e(I_valu("v_add_u32", vbl, PLANE_B, vbh, text=f"v_add_u32_e32 {vbl}, {PLANE_B}, {vbh}"))
+    else:
+        e(I_valu("v_add_u32", vbh, S_T0, V_RD_H, text=f"v_add_u32_e32 {vbh}, {S_T0}, {V_RD_H}"))
+        e(I_valu("v_add_u32", vbl, S_T0, V_RD_L, text=f"v_add_u32_e32 {vbl}, {S_T0}, {V_RD_L}"))
 
     # fragments of four k-steps in registers (three in flight ahead of the MFMAs: 96 matrix-pipe cycles per k-step do not cover
     # an LDS round trip): hi in XH[b][nt], lo in XL / XL2
@@ -871,7 +952,10 @@ def prologue():
     e(I_salu("s_add_u32", S(46), S(46), 64, scc=True)); e(I_salu("s_addc_u32", S(47), S(47), 0, scc=True))
     # lane = tid & 63; l31 = lane & 31; h = lane >> 5
     lane, l31, h = V(T0), V(T0 + 1), V(T0 + 2)
-    e(I_valu("v_and_b32", lane, 63, V_TMP)); e(I_valu("v_and_b32", l31, 31, V_TMP)); e(I_valu("v_lshrrev_b32", h, 5, lane))
+    if SHAPE == 16:         # l31 := c = lane & 15, h := g = lane >> 4: the bases below become c LDH_B + 16 g / + 8 g + 128 wave / 256 wave + 16 g
+        e(I_valu("v_and_b32", lane, 63, V_TMP)); e(I_valu("v_and_b32", l31, 15, V_TMP)); e(I_valu("v_lshrrev_b32", h, 4, lane))
+    else:
+        e(I_valu("v_and_b32", lane, 63, V_TMP)); e(I_valu("v_and_b32", l31, 31, V_TMP)); e(I_valu("v_lshrrev_b32", h, 5, lane))
     e(I_valu("v_lshlrev_b32", V_LANE16, 4, lane))
     # rd_h = lds + l31 * 528 + 16 h ; rd_l = rd_h + PLANE
     e(I_valu("v_mul_u32_u24", V_RD_H, LDH_B, l31))
@@ -985,14 +1069,15 @@ def range_flag_tail():
             I_label("L_range_done")]
 
 
-def build(save=False):
-    """-> (pre-issue statement, main statement, bodies); save: the training-forward body (see SAVE)"""
-    global SAVE
-    SAVE = bool(save)
+def build(save=False, shape=32):
+    """-> (pre-issue statement, main statement, bodies); save: the training-forward body (see SAVE); shape: 32 | 16 (see SHAPE)"""
+    global SAVE, SHAPE
+    assert shape in (32, 16) and not (save and shape == 16)
+    SAVE, SHAPE = bool(save), shape
     try:
         return _build()
     finally:
-        SAVE = False
+        SAVE, SHAPE = False, 32
 
 
 def _build():
@@ -1013,8 +1098,9 @@ def _build():
     }
     # the sigma ride of a view-direction static trunk: the last trunk layer's B phase and the A phase behind it (round 6: in the SAVE
     # build too -- the reference's documented training configuration, README.md:226-233, is a view-direction model)
-    bodies["B16RS"] = phase_body("B16RS", "B", 16, ride="epi_sig_ws", refills=True, tail_init=True, one_stream=True, copy=cp)
-    bodies["A16RS"] = phase_body("A16RS", "A", 16, ride="epi_sig", tail_init=True, vm_mode="formula", copy=cp)
+    if SHAPE != 16:         # (launches with the sigma ride keep the 32-shape body)
+        bodies["B16RS"] = phase_body("B16RS", "B", 16, ride="epi_sig_ws", refills=True, tail_init=True, one_stream=True, copy=cp)
+        bodies["A16RS"] = phase_body("A16RS", "A", 16, ride="epi_sig", tail_init=True, vm_mode="formula", copy=cp)
     if SAVE:
         bodies["SAVE_LAST"] = save_last_body()
     else:
@@ -1046,6 +1132,82 @@ def render(prog):
     return "\n".join(lines) + "\n"
 
 
+# ---- the compact form of the 16-shape file (render16): its nine commonest instructions as one-line macros whose register ranges are
+# assembler expressions ("v[128:128+3]"), several statements per source line -- the committed file stays a quarter of the plain
+# form's size.  Every macro call is expanded here again and compared with the instruction's own text, so the file assembles to
+# exactly the stream that was linted and simulated.
+MACROS16 = {
+    "QM": "v_mfma_f32_16x16x32_f16 v[{0}:{0}+3], a[{1}:{1}+3], v[{2}:{2}+3], v[{0}:{0}+3]",
+    "QR": "ds_read_b128 v[{0}:{0}+3], v{1} offset:{2}",
+    "QW": "ds_write_b64 v{0}, v[{1}:{1}+1] offset:{2}",
+    "QG": "global_load_dwordx4 a[{0}:{0}+3], v{1}, s[40:41] offset:{2}",
+    "QX": "v_max_f32 v{0}, 0, v{0}",
+    "QC": "v_cvt_pkrtz_f16_f32 v{0}, v{1}, v{2}",
+    "QL": "v_fma_mix_f32 v{0}, v{1}, -1.0, v{2} op_sel_hi:[1,0,0]",
+    "QH": "v_fma_mix_f32 v{0}, v{1}, -1.0, v{2} op_sel:[1,0,0] op_sel_hi:[1,0,0]",
+    "Q3": "v_max3_f32 v{0}, v{1}, v{2}, v{3}",
+}
+
+
+def expand16(name, args):
+    """the assembly text of a macro call, register-range expressions evaluated"""
+    import re
+    return re.sub(r"(\d+)\+(\d)\b", lambda m_: str(int(m_.group(1)) + int(m_.group(2))), MACROS16[name].format(*args))
+
+
+def macro_call16(ins):
+    """(macro name, integer arguments) of an instruction one of MACROS16 renders exactly, else None"""
+    a = ins.args
+    try:
+        call = {"mfma16": lambda: ("QM", [a["d"].i, a["a"].i, a["b"].i]),
+                "ds_read_b128": lambda: ("QR", [a["d"].i, a["addr"].i, a["off"]]),
+                "ds_write_b64": lambda: ("QW", [a["addr"].i, a["data"].i, a["off"]]),
+                "gload_s": lambda: ("QG", [a["d"].i, a["voff"].i, a["off"]]),
+                "v_max_f32": lambda: ("QX", [a["d"].i]),
+                "v_cvt_pkrtz_f16_f32": lambda: ("QC", [a["d"].i, a["s"][0].i, a["s"][1].i]),
+                "v_fma_mix_lo": lambda: ("QL", [a["d"].i, a["s"][0].i, a["s"][1].i]),
+                "v_fma_mix_hi": lambda: ("QH", [a["d"].i, a["s"][0].i, a["s"][1].i]),
+                "v_max3_f32": lambda: ("Q3", [a["d"].i] + [x.i for x in a["s"]])}[ins.op]()
+    except (KeyError, AttributeError, TypeError):
+        return None
+    return call if expand16(*call) == ins.text else None
+
+
+def render16(prog, width=150):
+    """the statement as source lines of macro calls and string literals (see MACROS16)"""
+    items = []
+    for ins in prog:
+        t = ins.text
+        if ins.kind == "label":
+            t = t.replace("L_", "L_h3a_%=_")
+        elif ins.kind == "branch":
+            t = t.replace(" L_", " L_h3a_%=_")
+        call = macro_call16(ins) if ins.kind not in ("label", "branch") else None
+        if call is not None:
+            items.append(f"{call[0]}({','.join(str(a) for a in call[1])})")
+        else:
+            items.append('"' + t + '\\n\\t"')
+    lines, cur = [], "   "
+    for it in items:
+        if len(cur) + 1 + len(it) > width and cur.strip():
+            lines.append(cur)
+            cur = "   "
+        cur += " " + it
+    lines.append(cur)
+    return "\n".join(lines) + "\n"
+
+
+def macro_defs16():
+    import re
+    out = ""
+    for name, tpl in MACROS16.items():
+        n_args = 1 + max(int(k) for k in re.findall(r"\{(\d)\}", tpl))
+        params = ",".join("abcd"[k] for k in range(n_args))
+        body = " ".join(('#' + "abcd"[int(p[1])]) if re.fullmatch(r"\{\d\}", p) else '"' + p + '"' for p in re.split(r"(\{\d\})", tpl + "\\n\\t") if p)
+        out += f"#define {name}({params}) {body}\n"
+    return out
+
+
 def lint(bodies, prog):
     errs = []
     for name, ins in bodies.items():
@@ -1072,7 +1234,8 @@ def main():
     timing, TIMING = TIMING, False               # (the stamps are the inference body's: `make timing` measures that one)
     _, prog_save, bodies_save = build(save=True)
     TIMING = timing
-    errs = lint(bodies, prog) + lint(bodies_save, prog_save)
+    _, prog16, bodies16 = build(shape=16)
+    errs = lint(bodies, prog) + lint(bodies_save, prog_save) + lint(bodies16, prog16)
     for e_ in errs[:40]:
         print("LINT:", e_)
     if errs:
@@ -1090,6 +1253,18 @@ def main():
     consts = "".join(f"#define H3A_BODY_{k} {v}\n" for k, v in BODY.items())
     consts += f"#define H3A_F_INIT {1 << F_INIT}\n#define H3A_F_REBUILD_T {1 << F_REBUILD_T}\n#define H3A_F_REBUILD {1 << F_REBUILD}\n"
     macro = lambda name, insts: f"#define {name} \\\n" + render(insts).replace("\n", " \\\n").rstrip(" \\\n") + "\n"
+    # the 16-shape body (build(shape=16)) first: nsff_field_kernel_h3a16 includes it beside the file below and shares H3A_PRE* and the
+    # clobber list; committed like the file below, in the compact form of render16
+    if not EXP and "H3A_RIDE_CAP" not in os.environ and NOSWAP_STORES:
+        out16 = os.path.join(os.path.dirname(out), "field_h3a16_body_timing.inc" if TIMING else "field_h3a16_body.inc")
+        with open(out16, "w") as f:
+            f.write("// GENERATED by tools/h3asm/gen.py -- do not edit.  H3A16_BODY: the trunk body of nsff_field_kernel_h3a16 -- the schedule of\n"
+                    "// H3A_BODY (field_h3a_body.inc) on v_mfma_f32_16x16x32_f16; same operands, same registers, weights in the 16-shape order.\n"
+                    "// Compact form: QM .. Q3 below are single instructions (register ranges as assembler expressions), several per line.\n" +
+                    macro_defs16() + "#define H3A16_CLOBBERS H3A_CLOBBERS\n#define H3A16_BODY \\\n" +
+                    render16(prog16).replace("\n", " \\\n").rstrip(" \\\n") + "\n")
+        print(f"wrote {os.path.normpath(out16)}: {sum(1 for i in prog16 if i.kind not in ('label', 'other'))} instructions, "
+              f"{sum(1 for i in prog16 if i.kind == 'mfma')} MFMAs")
     # the same 32 loads as eight statements, one weight slot each, for the kernel to spread over its encoder: statement k takes
     # %[pk] s64, %[off] s32 = (k < n1 ? r1 + wave r1w : r2 + wave r2w) + 4096 k, %[lane16] v32 = 16 (tid & 63)
     slots = ""

@@ -85,6 +85,15 @@ def I_mfma(d, a, b, c):
     return Inst("mfma", f"v_mfma_f32_32x32x16_f16 {d}, {a}, {b}, {_src(c)}", rd, [d], "mfma", dict(d=d, a=a, b=b, c=c))
 
 
+def I_mfma16(d, a, b, c):
+    """v_mfma_f32_16x16x32_f16 D(4), A(4), B(4), C(4 or the inline constant 0): 4 passes.  With g = lane >> 4, c = lane & 15: half t of
+    a lane's A (B) operand is row (column) c at k = 8 g + t; register e of D is row 4 g + e at column c.  Wait states: the lint applies
+    the 8-pass figures of the 32x32x16 form to it (MFMA_TO_VALU_STATES), which are never too weak for a 4-pass instruction."""
+    assert d.n == 4 and a.n == 4 and b.n == 4
+    rd = [a, b] + ([c] if _is_reg(c) else [])
+    return Inst("mfma16", f"v_mfma_f32_16x16x32_f16 {d}, {a}, {b}, {_src(c)}", rd, [d], "mfma", dict(d=d, a=a, b=b, c=c))
+
+
 def I_ds_read_b128(d, addr, off=0):
     assert 0 <= off < 65536 and d.n == 4
     return Inst("ds_read_b128", f"ds_read_b128 {d}, {addr} offset:{off}", [addr], [d], "lds_r", dict(d=d, addr=addr, off=off))
@@ -521,6 +530,22 @@ class Sim:
         if k == "mfma":
             w.n_mfma += 1
             d, A_, B_, C_ = a["d"], a["a"], a["b"], a["c"]
+            if ins.op == "mfma16":
+                def frag16(reg):     # (4 regs, NL) u32 -> [16 rows][32 k] f32:  lane l: row l%16, k = 8*(l//16) + t
+                    m = np.zeros((16, 32), np.float32)
+                    for r4 in range(4):
+                        lo, hi = halfs_of(self._rv(w, reg, r4))
+                        for g in range(4):
+                            m[:, 8 * g + 2 * r4] = lo[16 * g:16 * g + 16]
+                            m[:, 8 * g + 2 * r4 + 1] = hi[16 * g:16 * g + 16]
+                    return m
+                prod = frag16(A_).astype(np.float64) @ frag16(B_).astype(np.float64).T      # [i][j]
+                for r in range(4):   # register r of lane l: row 4 (l // 16) + r, column l % 16
+                    acc = np.zeros(NL, np.float32) if not isinstance(C_, Reg) else self._rv(w, C_, r).view(np.float32).copy()
+                    for g in range(4):
+                        acc[16 * g:16 * g + 16] = (acc[16 * g:16 * g + 16].astype(np.float64) + prod[4 * g + r, :]).astype(np.float32)
+                    self._wv(w, d, acc.view(np.uint32), r, masked=False)
+                return None
 
             def frag(reg):       # (4 regs, NL) u32 -> [32 rows][16 k] f32:  lane l: row l%32, k = 8*(l//32) + t
                 m = np.zeros((32, 16), np.float32)
