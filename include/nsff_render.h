@@ -1034,6 +1034,48 @@ int         nsff_field_launch_plan(const NsffModelDesc* desc, const NsffFieldArg
  * and, clear != 0, zeroes it (atomically: a bit set concurrently is either reported or kept). */
 int         nsff_range_flags(uint32_t* out, int32_t clear, void* stream);
 
+/* ---- LPIPS 0.1, net='alex', spatial=True (reference metrics.py:36-49, eval.py:176-178, 235-255).  DESIGN.md section 11. ----
+ * The graph: x = 2 x - 1 when `normalize`; (x - shift) / scale per channel; AlexNet `features` with its five ReLU outputs tapped
+ * (conv 3->64 k11 s4 p2 | maxpool 3 s2, conv 64->192 k5 p2 | maxpool 3 s2, conv 192->384 k3 p1 | conv 384->256 k3 p1 |
+ * conv 256->256 k3 p1); per tap  sum_c lin[c] (n0[c] - n1[c])^2  of the channel-normalised features n = f / (|f| + 1e-10);
+ * bilinear upsampling (align_corners = False) of the five maps to (H, W), and their sum.  fp32 operands and accumulation on the
+ * fp32 MFMA.  The library holds no trained values: the caller supplies the 15 tensors. */
+#define NSFF_LPIPS_MIN_SIZE  31   /* smallest H and W: below it the second pooling has no output pixel */
+
+/* The 15 fp32 device tensors in torch's layouts: conv_w[l] (cout, cin, k, k), conv_b[l] (cout), lin[l] (cout) for the five
+ * layers above.  nsff_lpips_pack writes them into `packed` (nsff_lpips_packed_bytes bytes, 16-byte aligned) in the order the
+ * convolution kernels stream: per layer the weights as [cout / 64][k][64] with k = (ky, kx, c), c fastest (the first layer's 33
+ * (kx, c) of a kernel row padded to 36 with zeros), then the bias and the lin vector.  Five small launches on `stream`. */
+typedef struct NsffLpipsWeights {
+    const float* conv_w[5];  const float* conv_b[5];  const float* lin[5];
+} NsffLpipsWeights;
+int64_t nsff_lpips_packed_bytes(void);
+int     nsff_lpips_pack(const NsffLpipsWeights* weights, float* packed, void* stream);
+
+/* hw[2 l], hw[2 l + 1] = height and width of tap l's feature map for an H x W image (288 x 512: 71 x 127, 35 x 63, 17 x 31
+ * three times); NSFF_ERR_INVALID below NSFF_LPIPS_MIN_SIZE.  Host only. */
+int     nsff_lpips_dims(int32_t H, int32_t W, int32_t* hw);
+
+/* n_frames image pairs gt / pred (F, H, W, 3) fp32, HWC, contiguous -- one batch of 2 F images, the launch count does not
+ * depend on F.  Outputs (at least one):
+ *   map   (F, H*W) fp32   the spatial LPIPS map;
+ *   sums  (F, 3) fp64     per frame: sum of the map over all pixels, the same over the pixels with valid != 0, and the number
+ *                         of those pixels (valid (F, H*W) uint8 or NULL = none selected; valid needs sums).  Added in a fixed
+ *                         order that depends on H * W alone: a frame's numbers are the same bits alone or in a batch.
+ * workspace: nsff_lpips_workspace_bytes bytes (0 = the shape is refused), 16-byte aligned, any content; one call at a time per
+ * workspace.  Refused before any launch: H or W below NSFF_LPIPS_MIN_SIZE, H * W >= 2^31, n_frames outside 1 .. 32767, no output,
+ * a workspace that is too small (NSFF_ERR_INVALID); a missing gt / pred / packed / workspace (NSFF_ERR_NULL); NSFF_ERR_ALIGN.
+ * Asynchronous on `stream`, allocates nothing, capturable. */
+typedef struct NsffLpipsArgs {
+    int32_t n_frames, H, W, normalize;
+    const float* gt;  const float* pred;  const uint8_t* valid;
+    const float* packed;
+    float* map;  double* sums;
+    void* workspace;  int64_t workspace_bytes;
+} NsffLpipsArgs;
+int64_t nsff_lpips_workspace_bytes(int32_t n_frames, int32_t H, int32_t W);
+int     nsff_lpips(const NsffLpipsArgs* args, void* stream);
+
 int         nsff_abi_version(void);
 const char* nsff_last_hip_error(void);
 

@@ -169,6 +169,16 @@ class SsimArgs(C.Structure):
                 ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+class LpipsWeights(C.Structure):
+    _fields_ = [("conv_w", _fp * 5), ("conv_b", _fp * 5), ("lin", _fp * 5)]
+
+
+class LpipsArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("normalize", C.c_int32),
+                ("gt", _fp), ("pred", _fp), ("valid", _fp), ("packed", _fp), ("map", _fp), ("sums", _fp),
+                ("workspace", _fp), ("workspace_bytes", C.c_int64)]
+
+
 _FINISH_PTRS = ["rgb", "gt", "valid", "depth", "lut", "rgb_clipped", "rgb_u8", "sums", "depth_range", "depth_u8", "depth_rgb_u8"]
 
 
@@ -313,6 +323,11 @@ _SIGNATURES = {
     "nsff_mpi_composite": (C.c_int, [C.POINTER(MpiArgs), _fp]),
     "nsff_ssim_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_ssim": (C.c_int, [C.POINTER(SsimArgs), _fp]),
+    "nsff_lpips_packed_bytes": (C.c_int64, []),
+    "nsff_lpips_pack": (C.c_int, [C.POINTER(LpipsWeights), _fp, _fp]),
+    "nsff_lpips_dims": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "nsff_lpips_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_lpips": (C.c_int, [C.POINTER(LpipsArgs), _fp]),
     "nsff_frame_finish_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_frame_finish": (C.c_int, [C.POINTER(FrameFinishArgs), _fp]),
     "nsff_val_panels_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
@@ -1125,6 +1140,73 @@ def ssim(gt, pred, mask=None, map=None, mean_map=None, sums=None, scratch=None):
             raise RuntimeError(f"ssim: an output / mask has {t.numel()} elements, expected {n}")
     with torch.cuda.device(gt.device):
         _check(load().nsff_ssim(C.byref(a), _stream()), "nsff_ssim")
+
+
+LPIPS_MIN_SIZE = 31           # NSFF_LPIPS_MIN_SIZE
+LPIPS_CONV_SHAPES = ((64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3))
+
+
+def lpips_dims(H, W):
+    """((h, w),) * 5: the feature-map size of each of the five taps for an H x W image."""
+    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+        raise ValueError(f"lpips: a {H} x {W} image is below the smallest size AlexNet's second pooling leaves a pixel of "
+                         f"({LPIPS_MIN_SIZE} x {LPIPS_MIN_SIZE})")
+    hw = (C.c_int32 * 10)()
+    _check(load().nsff_lpips_dims(int(H), int(W), hw), "nsff_lpips_dims")
+    return tuple((hw[2 * l], hw[2 * l + 1]) for l in range(5))
+
+
+def lpips_workspace_bytes(n_frames, H, W):
+    return int(load().nsff_lpips_workspace_bytes(int(n_frames), int(H), int(W)))
+
+
+def lpips_pack(conv_w, conv_b, lin):
+    """nsff_lpips_pack: the five conv weights (cout, cin, k, k), biases (cout,) and lin vectors (cout,) -- contiguous fp32 GPU
+    tensors -- into a new packed buffer."""
+    for l, shape in enumerate(LPIPS_CONV_SHAPES):
+        for t, want, what in ((conv_w[l], shape, "weight"), (conv_b[l], shape[:1], "bias"), (lin[l], shape[:1], "lin weight")):
+            require_gpu_tensor(t, f"lpips: layer {l} {what}")
+            if tuple(t.shape) != want:
+                raise RuntimeError(f"lpips: layer {l} {what} has shape {tuple(t.shape)}, expected {want}")
+    dev = conv_w[0].device
+    packed = torch.empty(int(load().nsff_lpips_packed_bytes()) // 4, dtype=torch.float32, device=dev)
+    w = LpipsWeights()
+    for l in range(5):
+        w.conv_w[l] = _dptr(conv_w[l], torch.float32, "lpips: weight")
+        w.conv_b[l] = _dptr(conv_b[l], torch.float32, "lpips: bias")
+        w.lin[l] = _dptr(lin[l], torch.float32, "lpips: lin weight")
+    with torch.cuda.device(dev):
+        _check(load().nsff_lpips_pack(C.byref(w), packed.data_ptr(), _stream()), "nsff_lpips_pack")
+    return packed
+
+
+def lpips(packed, gt, pred, valid=None, map=None, sums=None, normalize=False, workspace=None):
+    """nsff_lpips on (F, H, W, 3) fp32 image pairs: the spatial map (F, H, W) and the per-frame sums (F, 3) fp64 [map, map over
+    valid, valid pixels] -- whichever outputs are given.  valid (F, H*W) bool / uint8.  workspace: uint8 tensor of
+    lpips_workspace_bytes() bytes (a fresh one when None)."""
+    require_gpu_tensor(gt, "lpips: image_gt")
+    require_gpu_tensor(pred, "lpips: image_pred")
+    if gt.dim() != 4 or gt.shape[-1] != 3 or pred.shape != gt.shape:
+        raise RuntimeError(f"lpips: need (F, H, W, 3) image pairs of one shape, got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    F, H, W = (int(v) for v in gt.shape[:3])
+    lpips_dims(H, W)                                             # refuses an image that is too small by name
+    if valid is not None and valid.dtype == torch.bool:
+        valid = valid.view(torch.uint8)
+    need = lpips_workspace_bytes(F, H, W)
+    if need == 0:
+        raise RuntimeError(f"lpips: {F} frames of {H} x {W} are outside what one call takes (1 .. 32767 frames, H * W < 2^31)")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=gt.device)
+    a = LpipsArgs(n_frames=F, H=H, W=W, normalize=int(bool(normalize)), gt=_dptr(gt, torch.float32, "lpips: image_gt"),
+                  pred=_dptr(pred, torch.float32, "lpips: image_pred"), valid=_dptr(valid, torch.uint8, "lpips: valid"),
+                  packed=_dptr(packed, torch.float32, "lpips: packed weights"), map=_dptr(map, torch.float32, "lpips: map"),
+                  sums=_dptr(sums, torch.float64, "lpips: sums"), workspace=_dptr(workspace, torch.uint8, "lpips: workspace"),
+                  workspace_bytes=workspace.numel())
+    for t, n in ((valid, F * H * W), (map, F * H * W), (sums, F * 3)):
+        if t is not None and t.numel() != n:
+            raise RuntimeError(f"lpips: an output / mask has {t.numel()} elements, expected {n}")
+    with torch.cuda.device(gt.device):
+        _check(load().nsff_lpips(C.byref(a), _stream()), "nsff_lpips")
 
 
 def frame_finish_scratch_bytes(n_frames, H, W):

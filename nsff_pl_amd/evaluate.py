@@ -18,7 +18,8 @@ and PSNR -- the renderer-side pieces of the reference's ``eval.py`` / ``datasets
                            ``test_fixview{X}_interp{Y}``: the split's camera path and times (:mod:`nsff_pl_amd.paths`), rays per
                            pose on demand, :func:`render_sequence`, and the 8-bit frames eval.py writes (eval.py:183-184, 213-214,
                            222-223; the depth image of ``save_depth``) finished on the GPU (``nsff_frame_finish``).
-* :class:`SequenceScores`, :func:`evaluate_split` -- the PSNR / SSIM table of split ``test`` (eval.py:173-176, 230-255).
+* :class:`SequenceScores`, :func:`evaluate_split` -- the PSNR / SSIM table of split ``test`` (eval.py:173-176, 230-255), with
+                           its LPIPS row when given an :class:`nsff_pl_amd.lpips.LPIPS` (eval.py:176-178, 235, 240).
 * :func:`flow_frames`, :class:`FlowScores` -- the flow panel of the reference's test.ipynb: the induced optical flow of every
                            training pose, its colour image beside the dataset's flow, and the end-point error (``nsff_flow_maps``).
 """
@@ -367,10 +368,16 @@ class SequenceScores:
     """The score arrays of eval.py's split ``test`` (:173-176, 230-255): PSNR and SSIM per frame over the whole image (column 0)
     and over ``mask == 0`` (column 1; 0 for a frame scored without a mask, NaN for a mask that leaves no pixel).  ``add`` runs
     one ``nsff_frame_finish`` and one ``nsff_ssim`` call per frame and keeps the values on the GPU; nothing is read back before
-    ``psnrs`` / ``ssims`` are asked for."""
+    ``psnrs`` / ``ssims`` are asked for.
 
-    def __init__(self):
+    With ``lpips_model`` (an :class:`nsff_pl_amd.lpips.LPIPS`) ``add`` also scores ``metrics.lpips`` on the clipped frame
+    (eval.py:235, 240: one ``nsff_lpips`` call for both columns), ``lpipss`` is the third (N, 2) array, ``means`` returns three
+    arrays, ``table`` ends with eval.py:255's line and ``save`` writes ``lpips.npy``; without one everything is as before."""
+
+    def __init__(self, lpips_model=None):
+        self.lpips_model = lpips_model
         self._rows = []                                        # per frame: (4,) fp32 GPU tensor [psnr, psnr_m, ssim, ssim_m]
+        self._lpips_rows = []                                  # per frame: (2,) fp32 GPU tensor [lpips, lpips_m]
         self._scratch = {}
         self.last = None                                       # finish_frames' outputs of the last frame added
 
@@ -389,6 +396,9 @@ class SequenceScores:
         _, s, sm = metrics.ssim_maps(gt, out['rgb_clipped'], valid)
         zero = torch.zeros_like(p)
         self._rows.append(torch.cat([p, zero if mask is None else pm, s, zero if mask is None else sm]))
+        if self.lpips_model is not None:
+            _, l, lm = metrics.lpips_frames(self.lpips_model, gt, out['rgb_clipped'], valid)
+            self._lpips_rows.append(torch.cat([l, zero if mask is None else lm]))
         self.last = out
         return out
 
@@ -408,39 +418,56 @@ class SequenceScores:
     def ssims(self):
         return self._table()[:, 2:4]
 
+    @property
+    def lpipss(self):
+        """(N, 2), eval.py's ``lpipss``; needs ``lpips_model``."""
+        if self.lpips_model is None:
+            raise AttributeError("SequenceScores: no lpipss without an lpips_model")
+        if not self._lpips_rows:
+            return np.zeros((0, 2))
+        return torch.stack(self._lpips_rows).double().cpu().numpy()
+
     def means(self):
-        """(mean_psnr (2,), mean_ssim (2,)): np.nanmean over the frames (eval.py:243-244)."""
-        return np.nanmean(self.psnrs, 0), np.nanmean(self.ssims, 0)
+        """(mean_psnr (2,), mean_ssim (2,)) -- and mean_lpips (2,) with an lpips_model: np.nanmean over the frames
+        (eval.py:243-245)."""
+        means = np.nanmean(self.psnrs, 0), np.nanmean(self.ssims, 0)
+        return means if self.lpips_model is None else means + (np.nanmean(self.lpipss, 0),)
 
     def table(self):
-        """The lines eval.py:251-254 prints."""
+        """The lines eval.py:251-254 prints, and :255 with an lpips_model."""
         return format_scores(*self.means())
 
     def save(self, dir_name):
         os.makedirs(dir_name, exist_ok=True)
         np.save(os.path.join(dir_name, 'psnr.npy'), self.psnrs)
         np.save(os.path.join(dir_name, 'ssim.npy'), self.ssims)
+        if self.lpips_model is not None:
+            np.save(os.path.join(dir_name, 'lpips.npy'), self.lpipss)
 
 
-def format_scores(mean_psnr, mean_ssim):
-    """eval.py:251-254 (without the LPIPS row): header, rule, PSNR row, SSIM row -- a list of lines."""
-    return ['Score \t Whole image  \t Dynamic only',
-            '-------------------------------------',
-            f'PSNR  \t {mean_psnr[0]:.4f} \t {mean_psnr[1]:.4f}',
-            f'SSIM  \t {mean_ssim[0]:.4f} \t {mean_ssim[1]:.4f}']
+def format_scores(mean_psnr, mean_ssim, mean_lpips=None):
+    """eval.py:251-254: header, rule, PSNR row, SSIM row -- a list of lines; with mean_lpips the LPIPS row of :255 as well."""
+    lines = ['Score \t Whole image  \t Dynamic only',
+             '-------------------------------------',
+             f'PSNR  \t {mean_psnr[0]:.4f} \t {mean_psnr[1]:.4f}',
+             f'SSIM  \t {mean_ssim[0]:.4f} \t {mean_ssim[1]:.4f}']
+    if mean_lpips is not None:
+        lines.append(f'LPIPS \t {mean_lpips[0]:.4f} \t {mean_lpips[1]:.4f}')
+    return lines
 
 
 def evaluate_split(models, embeddings, K, poses, img_wh, N_samples, N_importance, images_gt, masks=None, chunk=1024 * 32,
-                   sink=None, **kwargs):
+                   sink=None, lpips_model=None, **kwargs):
     """Render split ``test`` and score it against the ground truth in one loop (eval.py:181-240): images_gt (N,h,w,3) fp32 GPU
     frames (or a sequence of them), masks (N,h,w) or None.  ``sink(name, rgb_u8)`` receives every 8-bit frame (a GPU tensor of
-    the frame just scored) when given.  Returns the :class:`SequenceScores`."""
+    the frame just scored) when given.  lpips_model: an :class:`nsff_pl_amd.lpips.LPIPS` adds the LPIPS scores.  Returns the
+    :class:`SequenceScores`."""
     if len(images_gt) != len(poses) or (masks is not None and len(masks) != len(poses)):
         raise ValueError(f"evaluate_split: {len(poses)} poses need as many ground-truth frames"
                          f"{'' if masks is None else ' and masks'}, got {len(images_gt)}"
                          f"{'' if masks is None else ' and ' + str(len(masks))}")
     names, frames = _split_frames(models, embeddings, K, poses, 'test', img_wh, N_samples, N_importance, chunk, kwargs)
-    scores = SequenceScores()
+    scores = SequenceScores(lpips_model=lpips_model)
     for i, (name, (_, rgb, _)) in enumerate(zip(names, frames)):
         out = scores.add(images_gt[i], rgb, None if masks is None else masks[i])
         if sink is not None:

@@ -1,12 +1,15 @@
-"""The reference's quality metrics (metrics.py:6-33): ``mse``, ``psnr`` and ``ssim`` with the reference's signatures, and
-``ssim_maps`` for batches of frames.
+"""The reference's quality metrics (metrics.py:6-49): ``mse``, ``psnr``, ``ssim`` and ``lpips`` with the reference's signatures,
+and ``ssim_maps`` / ``lpips_frames`` for batches of frames.
 
 ``ssim`` is what the reference computes, which is NOT the standard SSIM: the reference calls kornia 0.5.4's
 ``ssim_loss(gt, pred, window_size=11, reduction='none')`` -- ``loss = clamp((1 - ssim) / 2, 0, 1)`` per pixel and channel --
 and returns ``1 - loss``, i.e. ``(1 + ssim) / 2`` wherever ssim >= -1 (so 0.5 where standard SSIM is 0).  The published
 numbers of BASELINE.md (0.9672 full frame, 0.9321 inside the dynamic mask) are on this scale.  The map, its reductions and
 the channel-mean map of hard sampling come from one HIP launch (``nsff_ssim``, csrc/metrics.hip); there is no CPU path.
-LPIPS (metrics.py:36-51) needs AlexNet weights and is not provided.
+
+``lpips`` (metrics.py:36-49) takes an :class:`nsff_pl_amd.lpips.LPIPS` as its ``lpips_model`` -- LPIPS 0.1, AlexNet, spatial,
+``normalize=True`` as the reference calls it -- and runs the network in one ``nsff_lpips`` call (csrc/lpips.hip).  The trained
+weights come from the caller; values on them are unpinned (the arithmetic is pinned on seeded random weights).
 
 ``finish_frames`` / ``psnr_frames`` are the per-frame finishing work of the reference's eval.py for F frames at once
 (``nsff_frame_finish``, csrc/metrics.hip): the clipped image, the 8-bit image eval.py writes, the squared-error sums behind
@@ -85,6 +88,41 @@ def ssim_maps(gt, pred, valid_mask=None, window_size=11):
     frame = (1 - sums[:, 0] / (3 * H * W)).float()
     frame_mask = None if mask is None else (1 - sums[:, 1] / (3 * sums[:, 2])).float()
     return 1 - loss, frame, frame_mask
+
+
+@torch.no_grad()
+def lpips(lpips_model, image_gt, image_pred, valid_mask=None, reduction='mean'):
+    """metrics.py:36-49: image_gt / image_pred (H, W, 3) fp32 in [0, 1] on the GPU, valid_mask (H, W) bool or None.
+
+    reduction='mean': the mean of the spatial map over the (masked) pixels -- a device scalar (fp32) from the kernel's fp64 sums,
+    no boolean indexing; NaN for a mask without a pixel, as the reference's mean of an empty selection.  Any other reduction:
+    the map (H, W), or its (n,) selection by valid_mask."""
+    if image_gt.dim() != 3 or image_gt.shape[-1] != 3:
+        raise RuntimeError(f"lpips: need (H, W, 3) images, got {tuple(image_gt.shape)}")
+    gt, pred = image_gt.unsqueeze(0), image_pred.unsqueeze(0)
+    H, W = int(gt.shape[1]), int(gt.shape[2])
+    if reduction != 'mean':
+        value, _ = lpips_model.score(gt, pred, normalize=True)
+        return value[0] if valid_mask is None else value[0][valid_mask]
+    _, sums = lpips_model.score(gt, pred, valid=None if valid_mask is None else valid_mask.reshape(1, H, W), want_map=False,
+                                want_sums=True, normalize=True)
+    if valid_mask is None:
+        return (sums[0, 0] / (H * W)).float()
+    return (sums[0, 1] / sums[0, 2]).float()
+
+
+@torch.no_grad()
+def lpips_frames(model, gt, pred, valid_mask=None):
+    """Batched form for F frames: gt / pred (F, H, W, 3) in [0, 1], valid_mask (F, H, W) or None, one ``nsff_lpips`` call whose
+    launch count does not depend on F.
+
+    Returns ``(lpips_map, frame_lpips, frame_lpips_mask)``: the spatial map (F, H, W), its mean per frame (F,), and the mean over
+    each frame's valid_mask (F,; None without a mask; NaN for a frame whose mask is empty) -- all fp32."""
+    F, H, W = (int(v) for v in gt.shape[:3])
+    value, sums = model.score(gt, pred, valid=valid_mask, want_sums=True, normalize=True)
+    frame = (sums[:, 0] / (H * W)).float()
+    frame_mask = None if valid_mask is None else (sums[:, 1] / sums[:, 2]).float()
+    return value, frame, frame_mask
 
 
 def _frames4(t, what, last):

@@ -22,6 +22,11 @@ The frame resize (--only resize) of 1 and 30 decoded 1280 x 720 frames to 512 x 
 nsff_frame_resize alone on preallocated outputs with the tables already on the device -- Lanczos on uint8 RGB, nearest on the
 uint8 mask and the fp32 disparity, bilinear on the fp32 flow.  Byte bound: every source byte read once plus every output byte
 written (the nearest kernels read fewer: a source pixel they skip is never touched, so their bound is an upper one).
+LPIPS (--only lpips) on 1 and 30 frame pairs (csrc/lpips.hip): nsff_lpips alone on preallocated outputs (map and sums), the whole
+LPIPS.score call, and -- in the same run, alternating with it -- the same graph in torch on the GPU (F.conv2d etc. through MIOpen,
+fp32, channels-first as the reference feeds it; seeded random weights of AlexNet's shapes): what a user has without this kernel.
+Bounds per call: the convolutions' FLOPs over the fp32 MFMA peak, and the bytes that must move (both images, the packed weights
+once, the map) over the HBM peak; `act_MB` is what the call actually writes and reads back as taps and pooled maps.
 """
 import argparse
 import json
@@ -33,10 +38,13 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from nsff_pl_amd import _lib, frames, metrics  # noqa: E402
+import torch.nn.functional as TF  # noqa: E402
+
+from nsff_pl_amd import LPIPS, _lib, frames, metrics  # noqa: E402
 from nsff_pl_amd.sampling import RayBank  # noqa: E402
 
 HBM_PEAK = 8.0e12          # B/s (MI355X datasheet)
+F32_MFMA_PEAK = 157.3e12   # FLOP/s, v_mfma_f32_32x32x2_f32 (MI355X datasheet: the fp32 vector rate)
 
 
 def time_us(fn, reps, warmup=5):
@@ -169,10 +177,79 @@ def bench_resize(dev, g, W, H, reps, F, src_wh=(1280, 720)):
     return res
 
 
+def time_alternating_us(fns, reps, warmup=5):
+    """Median device time of each of fns, taken in turn within every repetition (they see the same machine state)."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[i].append(a.elapsed_time(b) * 1e3)
+    return [sorted(t)[len(t) // 2] for t in times]
+
+
+LPIPS_CONV = ((3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1))   # cin, cout, k, stride, pad
+LPIPS_LAUNCHES = 10        # nsff_lpips: one memset node, five convolutions, two pools, the distance and the final pass
+
+
+def torch_lpips(in0, in1, conv_w, conv_b, lin):
+    """The LPIPS graph (normalize=True, spatial=True) on (F, 3, H, W) fp32 batches with torch's own kernels."""
+    shift = in0.new_tensor([-.030, -.088, -.188]).view(1, 3, 1, 1)
+    scale = in0.new_tensor([.458, .448, .450]).view(1, 3, 1, 1)
+    x = torch.cat([(2 * in0 - 1 - shift) / scale, (2 * in1 - 1 - shift) / scale])
+    F, H, W = in0.shape[0], in0.shape[2], in0.shape[3]
+    total = 0
+    for l, (_, _, _, stride, pad) in enumerate(LPIPS_CONV):
+        if l in (1, 2):
+            x = TF.max_pool2d(x, 3, 2)
+        x = TF.relu(TF.conv2d(x, conv_w[l], conv_b[l], stride=stride, padding=pad))
+        n = x / (torch.sqrt(torch.sum(x ** 2, dim=1, keepdim=True)) + 1e-10)
+        m = TF.conv2d((n[:F] - n[F:]) ** 2, lin[l])
+        total = total + TF.interpolate(m, size=(H, W), mode="bilinear", align_corners=False)
+    return total
+
+
+def bench_lpips(dev, g, W, H, reps, F):
+    conv_w = [torch.randn(cout, cin, k, k, device=dev, generator=g) * (2.0 / (cin * k * k)) ** 0.5 for cin, cout, k, _, _ in LPIPS_CONV]
+    conv_b = [torch.rand(cout, device=dev, generator=g) * 0.1 - 0.05 for _, cout, _, _, _ in LPIPS_CONV]
+    lin = [torch.rand(1, cout, 1, 1, device=dev, generator=g) / cout for _, cout, _, _, _ in LPIPS_CONV]
+    model = LPIPS(conv_w, conv_b, lin, device=dev)
+    gt = torch.rand(F, H, W, 3, device=dev, generator=g)
+    pred = (gt + 0.05 * torch.randn(F, H, W, 3, device=dev, generator=g)).clamp(0, 1)
+    valid = torch.rand(F, H, W, device=dev, generator=g) < 0.7
+    gt_chw, pred_chw = gt.permute(0, 3, 1, 2).contiguous(), pred.permute(0, 3, 1, 2).contiguous()
+    out_map = torch.empty(F, H, W, device=dev)
+    sums = torch.empty(F, 3, dtype=torch.float64, device=dev)
+    work = torch.empty(_lib.lpips_workspace_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    packed = model.packed()
+    launch = lambda: _lib.lpips(packed, gt, pred, valid=valid.reshape(F, H * W), map=out_map, sums=sums, normalize=True, workspace=work)
+    whole = lambda: model.score(gt, pred, valid=valid, want_sums=True, normalize=True)
+    ref = lambda: torch_lpips(gt_chw, pred_chw, conv_w, conv_b, lin)
+    launch()
+    worst = (out_map - ref()[:, 0]).abs().max().item()           # the two forms being timed compute the same thing
+    t_launch, t_whole, t_ref = time_alternating_us((launch, whole, ref), reps)
+    dims = _lib.lpips_dims(H, W)
+    flops = sum(2 * F * 2 * h * w * cout * cin * k * k for (h, w), (cin, cout, k, _, _) in zip(dims, LPIPS_CONV))
+    pooled = [((h - 3) // 2 + 1) * ((w - 3) // 2 + 1) for h, w in dims[:2]]
+    act = 4 * 2 * F * (sum(h * w * c[1] for (h, w), c in zip(dims, LPIPS_CONV)) + sum(p * c[1] for p, c in zip(pooled, LPIPS_CONV)))
+    must = F * H * W * (2 * 12 + 4 + 1) + packed.numel() * 4 + F * 24
+    return {f"lpips_F{F}_launch_us": t_launch, f"lpips_F{F}_score_us": t_whole, f"lpips_F{F}_torch_us": t_ref,
+            f"lpips_F{F}_launches": LPIPS_LAUNCHES, f"lpips_F{F}_gflop": flops / 1e9,
+            f"lpips_F{F}_flop_bound_us": flops / F32_MFMA_PEAK * 1e6, f"lpips_F{F}_byte_bound_us": must / HBM_PEAK * 1e6,
+            f"lpips_F{F}_act_MB": act / 1e6, f"lpips_F{F}_max_abs_diff_vs_torch": worst}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize (default: everything)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips (default: everything but lpips)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -194,7 +271,11 @@ def main():
             for F in (1, 30):
                 out.update(bench_resize(dev, g, W, H, args.reps, F))
                 torch.cuda.empty_cache()
-        print(json.dumps({k: round(v, 2) if isinstance(v, float) else v for k, v in out.items()}))
+        if "lpips" in only:
+            for F in (1, 30):
+                out.update(bench_lpips(dev, g, W, H, args.reps, F))
+                torch.cuda.empty_cache()
+        print(json.dumps({k: (round(v, 2) if v >= 0.01 else float(f"{v:.3g}")) if isinstance(v, float) else v for k, v in out.items()}))
         return
     gt = torch.rand(H, W, 3, device=dev, generator=g)
     pred = (gt + 0.05 * torch.randn(H, W, 3, device=dev, generator=g)).clamp(0, 1)
