@@ -1076,6 +1076,46 @@ typedef struct NsffLpipsArgs {
 int64_t nsff_lpips_workspace_bytes(int32_t n_frames, int32_t H, int32_t W);
 int     nsff_lpips(const NsffLpipsArgs* args, void* stream);
 
+/* ---- the scene scale from COLMAP points and mono-depth disparities (csrc/scale.hip): the per-pixel and
+ * per-point work of the reference's nearest_depth loop, datasets/monocular.py:93-116, for all frames at once.  The O(F) rest --
+ * slope, intercept, r^2, numpy's percentile interpolation, the r^2 branch, the minimum and the factor 0.75 -- is the caller's
+ * (nsff_pl_amd/scene.py does it in numpy float64).
+ * Inputs, all DEVICE memory:
+ *   points (N, 3) fp64   COLMAP world points;                vis (F, N) uint8   1 where point i is visible in frame f;
+ *   w2c (F, 3, 4) fp64   COLMAP world-to-camera [R | t];     K (3, 3) fp32      its nine values are converted to double as they are;
+ *   disps (F, H, W) fp32 disparities at the training resolution.
+ * The point pass (fp64, uncontracted): c = R p + t, uvd = K c, u = uvd.x / uvd.z, v = uvd.y / uvd.z, truncated toward zero and
+ * clamped into the image (astype(int), then np.clip), x = 1 / uvd.z, y = (double)disps[f][v][u].  Points behind the camera are
+ * not excluded (the reference does not).  A visible point with a non-finite u, v or x counts in n_nonfinite and is left out of
+ * the moments.  Outputs:
+ *   stats (F, 8) fp64     [n_vis, n_nonfinite, mean_x, mean_y, sxx, sxy, syy, n_nan_disp]: the means and the mean-centred sums
+ *                         sum (x - mean_x)^2, sum (x - mean_x)(y - mean_y), sum (y - mean_y)^2 over the n_vis - n_nonfinite
+ *                         points, from per-workgroup two-pass moments merged as (n, mean, M2) triples in a fixed order that
+ *                         depends on N alone: a frame's numbers are the same bits alone or in a batch.  n_nan_disp: NaNs among
+ *                         the frame's H * W disparities;
+ *   disp_os (F, 2) fp32   the frame's disparities of ascending rank disp_rank[0] and disp_rank[1] (0-based; NaNs are not ranked,
+ *                         -0 ranks as and comes back as +0; a rank beyond the ranked population gives NaN);
+ *   depth_os (F, 2) fp64  the visible points' camera depths uvd.z of rank lo = floor((n_vis - 1) * 0.05) and min(lo + 1, n_vis - 1),
+ *                         the product formed on the device in double (+inf where n_vis = 0);
+ *                         unspecified for a frame with n_nonfinite > 0: a NaN depth is ranked by its bits;
+ *   pix (F, N) int32      optional: the flat pixel index v * W + u a visible point gathered from, -1 not visible, -2 non-finite.
+ * Both selections are exact radix selects (8-bit digits, most significant first, of an order-preserving 32- / 64-bit key;
+ * integer histograms, so nothing depends on the launch order).
+ * work: nsff_scene_scale_work_bytes bytes (0 = the shape is refused), 16-byte aligned, any content before a call; its counters
+ * are zero again after it; one call at a time per workspace.  Refused before any launch: n_frames outside 1 .. 65535, H * W >= 2^31,
+ * n_points < 1, a rank outside [0, H * W), a workspace that is too small (NSFF_ERR_INVALID); a missing pointer other than pix
+ * (NSFF_ERR_NULL); fp64 arrays and work not 8- / 16-byte, fp32 / int32 arrays not 4-byte aligned (NSFF_ERR_ALIGN).
+ * Asynchronous on `stream`, allocates nothing, capturable. */
+typedef struct NsffSceneScaleArgs {
+    int32_t n_frames, n_points, H, W;
+    int32_t disp_rank[2];
+    const double* points;  const uint8_t* vis;  const double* w2c;  const float* K;  const float* disps;
+    double* stats;  float* disp_os;  double* depth_os;  int32_t* pix;
+    void* work;  int64_t work_bytes;
+} NsffSceneScaleArgs;
+int64_t nsff_scene_scale_work_bytes(int32_t n_frames, int32_t n_points, int32_t H, int32_t W);
+int     nsff_scene_scale(const NsffSceneScaleArgs* args, void* stream);
+
 int         nsff_abi_version(void);
 const char* nsff_last_hip_error(void);
 

@@ -20,10 +20,13 @@ from .flow import induced_flow, flow_to_image, flow_epe, epe_from_sums
 from . import panels
 from .panels import validation_panels, error_blend
 from .lpips import LPIPS
+from . import scene
+from .scene import nearest_depth, scene_from_colmap, visibility_matrix
 
 __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "set_precision", "get_precision",
            "set_range_check", "get_range_check", "range_flags", "RangeFlags",
            "build_records", "projection_matrices", "RayBank",
            "resize_images", "resize_masks", "resize_disps", "resize_flows", "resize_frames", "scaled_intrinsics",
            "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
-           "panels", "validation_panels", "error_blend", "LPIPS"]
+           "panels", "validation_panels", "error_blend", "LPIPS",
+           "scene", "nearest_depth", "scene_from_colmap", "visibility_matrix"]

@@ -241,6 +241,12 @@ class FrameResizeArgs(C.Structure):
                 ("x_start", _fp), ("x_count", _fp), ("x_weights", _fp), ("y_start", _fp), ("y_count", _fp), ("y_weights", _fp)]
 
 
+class SceneScaleArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("n_points", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("disp_rank", C.c_int32 * 2), ("points", _fp), ("vis", _fp), ("w2c", _fp), ("K", _fp), ("disps", _fp),
+                ("stats", _fp), ("disp_os", _fp), ("depth_os", _fp), ("pix", _fp), ("work", _fp), ("work_bytes", C.c_int64)]
+
+
 # name -> (restype, argtypes); also the list of symbols the header declares
 _SIGNATURES = {
     "nsff_abi_version": (C.c_int, []),
@@ -283,6 +289,8 @@ _SIGNATURES = {
     "nsff_resize_ksize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_resize_table": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nsff_frame_resize": (C.c_int, [C.POINTER(FrameResizeArgs), _fp]),
+    "nsff_scene_scale_work_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_scene_scale": (C.c_int, [C.POINTER(SceneScaleArgs), _fp]),
     "nsff_bwd_packed_bytes": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_size_t)]),
     "nsff_pack_weights_bwd": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(_fp), _fp, _fp]),
     "nsff_field_backward": (C.c_int, [C.POINTER(ModelDesc), _fp, C.POINTER(FieldBwdArgs), _fp]),
@@ -1433,6 +1441,48 @@ def frame_resize(filter, src, dst, x_table, y_table, ratio=(1.0, 1.0)):
         setattr(a, f"ksize_{axis}", 1 if weights is None else int(weights.shape[1]))
     with torch.cuda.device(src.device):
         _check(load().nsff_frame_resize(C.byref(a), _stream()), "nsff_frame_resize")
+
+
+def scene_scale_work_bytes(n_frames, n_points, H, W):
+    """nsff_scene_scale_work_bytes: the workspace of one scene_scale call in bytes, 0 where the shape is refused."""
+    return int(load().nsff_scene_scale_work_bytes(int(n_frames), int(n_points), int(H), int(W)))
+
+
+def scene_scale(points, vis, w2c, K, disps, disp_rank, want_pix=False, work=None, out=None):
+    """nsff_scene_scale on contiguous GPU tensors: points (N,3) fp64, vis (F,N) uint8, w2c (F,3,4) fp64, K (3,3) fp32, disps
+    (F,H,W) fp32; disp_rank: the two 0-based ranks of the disparity order statistics.  Returns (stats (F,8) fp64, disp_os (F,2)
+    fp32, depth_os (F,2) fp64, pix (F,N) int32 or None) on the device.  work: a uint8 GPU tensor of scene_scale_work_bytes()
+    bytes with any content (a fresh one when None); out: write into these four tensors (pix may be None) instead of new ones."""
+    require_gpu_tensor(disps, "scene_scale: disps")
+    if disps.dim() != 3 or vis.dim() != 2 or points.dim() != 2:
+        raise RuntimeError(f"scene_scale: need disps (F,H,W), vis (F,N) and points (N,3), got {tuple(disps.shape)}, "
+                           f"{tuple(vis.shape)} and {tuple(points.shape)}")
+    (F, H, W), N, dev = (int(v) for v in disps.shape), int(points.shape[0]), disps.device
+    if tuple(points.shape) != (N, 3) or tuple(vis.shape) != (F, N) or tuple(w2c.shape) != (F, 3, 4) or tuple(K.shape) != (3, 3):
+        raise RuntimeError(f"scene_scale: points {tuple(points.shape)}, vis {tuple(vis.shape)}, w2c {tuple(w2c.shape)}, K "
+                           f"{tuple(K.shape)} do not go with {F} frames of {N} points")
+    need = scene_scale_work_bytes(F, N, H, W)
+    if work is None and need > 0:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    if out is not None:
+        stats, disp_os, depth_os, pix = out
+        if (stats.numel(), disp_os.numel(), depth_os.numel()) != (8 * F, 2 * F, 2 * F) or (pix is not None and pix.numel() != F * N):
+            raise RuntimeError(f"scene_scale: out must be (F,8), (F,2), (F,2) and (F,N) or None for F = {F}, N = {N}")
+    else:
+        stats = torch.empty(F, 8, dtype=torch.float64, device=dev)
+        disp_os = torch.empty(F, 2, dtype=torch.float32, device=dev)
+        depth_os = torch.empty(F, 2, dtype=torch.float64, device=dev)
+        pix = torch.empty(F, N, dtype=torch.int32, device=dev) if want_pix else None
+    a = SceneScaleArgs(n_frames=F, n_points=N, H=H, W=W, disp_rank=(C.c_int32 * 2)(int(disp_rank[0]), int(disp_rank[1])),
+                       points=_dptr(points, torch.float64, "scene_scale: points"), vis=_dptr(vis, torch.uint8, "scene_scale: vis"),
+                       w2c=_dptr(w2c, torch.float64, "scene_scale: w2c"), K=_dptr(K, torch.float32, "scene_scale: K"),
+                       disps=_dptr(disps, torch.float32, "scene_scale: disps"), stats=_dptr(stats, torch.float64, "scene_scale: stats"),
+                       disp_os=_dptr(disp_os, torch.float32, "scene_scale: disp_os"),
+                       depth_os=_dptr(depth_os, torch.float64, "scene_scale: depth_os"), pix=_dptr(pix, torch.int32, "scene_scale: pix"),
+                       work=_dptr(work, torch.uint8, "scene_scale: work"), work_bytes=0 if work is None else work.numel())
+    with torch.cuda.device(dev):
+        _check(load().nsff_scene_scale(C.byref(a), _stream()), "nsff_scene_scale")
+    return stats, disp_os, depth_os, pix
 
 
 def range_flags(out, clear):

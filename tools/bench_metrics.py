@@ -27,12 +27,16 @@ LPIPS.score call, and -- in the same run, alternating with it -- the same graph 
 fp32, channels-first as the reference feeds it; seeded random weights of AlexNet's shapes): what a user has without this kernel.
 Bounds per call: the convolutions' FLOPs over the fp32 MFMA peak, and the bytes that must move (both images, the packed weights
 once, the map) over the HBM peak; `act_MB` is what the call actually writes and reads back as taps and pooled maps.
+The scene scale (--only scale) on 1, 30 and 100 frames of 512 x 288 disparities with 20 000 COLMAP points (csrc/scale.hip):
+nsff_scene_scale alone on preallocated outputs and workspace against the byte bound of each of its kernels (bench_scale states the
+arithmetic), the whole scene.nearest_depth call by the host clock, and the reference's per-frame numpy loop, restated in host_numpy_scale, on the same data on the host.
 """
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,7 +44,7 @@ sys.path.insert(0, ROOT)
 
 import torch.nn.functional as TF  # noqa: E402
 
-from nsff_pl_amd import LPIPS, _lib, frames, metrics  # noqa: E402
+from nsff_pl_amd import LPIPS, _lib, frames, metrics, scene  # noqa: E402
 from nsff_pl_amd.sampling import RayBank  # noqa: E402
 
 HBM_PEAK = 8.0e12          # B/s (MI355X datasheet)
@@ -246,10 +250,82 @@ def bench_lpips(dev, g, W, H, reps, F):
             f"lpips_F{F}_act_MB": act / 1e6, f"lpips_F{F}_max_abs_diff_vs_torch": worst}
 
 
+def host_numpy_scale(K, w2c, points, vis, disps):
+    """What the reference's nearest_depth loop (datasets/monocular.py:93-116) computes, per frame with numpy on the host, in this
+    project's words: project the frame's visible points, truncate and clamp to a pixel, fit disparity = slope / depth + intercept
+    by mean-centred moments, and take slope / (95th percentile of the frame - intercept) where r^2 > 0.9, else the 5th percentile
+    of the depths; 0.75 x the minimum."""
+    K64 = K.astype(np.float64)
+    best = 1e8
+    for f, frame in enumerate(disps):
+        H, W = frame.shape
+        seen = points[vis[f] == 1]
+        cam = w2c[f, :3, :3] @ seen.T + w2c[f, :3, 3:]
+        proj = K64 @ cam
+        depth = proj[2]
+        col = np.clip(np.trunc(proj[0] / depth), 0, W - 1).astype(np.int64)
+        row = np.clip(np.trunc(proj[1] / depth), 0, H - 1).astype(np.int64)
+        inv, y = 1.0 / depth, frame[row, col].astype(np.float64)
+        di, dy = inv - inv.mean(), y - y.mean()
+        sxx, sxy, syy = di @ di, di @ dy, dy @ dy
+        slope = sxy / sxx
+        intercept = y.mean() - slope * inv.mean()
+        if sxy * sxy > 0.9 * sxx * syy:
+            best = min(best, slope / (np.percentile(frame, 95) - intercept))
+        else:
+            best = min(best, np.percentile(depth, 5))
+    return 0.75 * best
+
+
+def bench_scale(dev, g, W, H, reps, F, N=20000):
+    """nsff_scene_scale (csrc/scale.hip) on F frames of W x H disparities and N points, 60 % visible per frame, on preallocated
+    outputs and workspace.  The byte bounds, per kernel:
+      clear   the tickets, partials and histograms written once:           workspace bytes - 8 F N
+      points  per frame N visibility bytes, N points (24 B), one gathered disparity (4 B), N depths written (8 B):  37 F N
+      disp    the disparities read once per digit pass:                    4 passes x 4 F H W
+      depth   the depth array read once per digit pass:                    8 passes x 8 F N
+    (the finish kernel moves 2 x 12 x 1 KiB of counters per frame, not counted).  The whole call is 15 launches; the time is the
+    call's, so the figure beside the bounds' sum includes their launch gaps.  The comparison is host_numpy_scale, the reference's per-frame numpy loop restated,
+    on the same data on the host (wall clock, one run)."""
+    import time
+    rng = np.random.default_rng(0)
+    depth = rng.uniform(2.0, 12.0, N)
+    f = 0.9 * W
+    K = np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], np.float32)
+    points = np.stack([rng.uniform(-0.55, 0.55, N) * depth * W / f, rng.uniform(-0.55, 0.55, N) * depth * H / f, depth], 1)
+    w2c = np.tile(np.eye(4), (F, 1, 1))
+    w2c[:, :3, 3] = rng.normal(size=(F, 3)) * 0.1
+    vis = (rng.random((F, N)) < 0.6).astype(np.uint8)
+    disps = torch.rand(F, H, W, device=dev, generator=g) * 0.6 + 0.1
+    t_points, t_vis = torch.from_numpy(points).to(dev), torch.from_numpy(vis).to(dev)
+    t_w2c, t_K = torch.from_numpy(np.ascontiguousarray(w2c[:, :3])).to(dev), torch.from_numpy(K).to(dev)
+    lo, hi, _ = scene.percentile_ranks(H * W, 95, np.float32)
+    work_bytes = _lib.scene_scale_work_bytes(F, N, H, W)
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+    outs = (torch.empty(F, 8, dtype=torch.float64, device=dev), torch.empty(F, 2, device=dev),
+            torch.empty(F, 2, dtype=torch.float64, device=dev), None)
+    call = lambda: _lib.scene_scale(t_points, t_vis, t_w2c, t_K, disps, (lo, hi), work=work, out=outs)
+    res = {f"scale_F{F}_us": time_us(call, reps)}
+    bounds = {"clear": work_bytes - 8 * F * N, "points": 37 * F * N, "disp_select": 4 * 4 * F * H * W, "depth_select": 8 * 8 * F * N}
+    for k, b in bounds.items():
+        res[f"scale_F{F}_{k}_bound_us"] = b / HBM_PEAK * 1e6
+    res[f"scale_F{F}_bound_us"] = sum(bounds.values()) / HBM_PEAK * 1e6
+    host_disps = disps.cpu().numpy()
+    t0 = time.perf_counter()
+    want = host_numpy_scale(K, w2c, points, vis, host_disps)
+    res[f"scale_F{F}_reference_host_us"] = (time.perf_counter() - t0) * 1e6
+    t0 = time.perf_counter()
+    got = scene.nearest_depth(K, w2c, points, vis, disps)
+    torch.cuda.synchronize()
+    res[f"scale_F{F}_nearest_depth_wall_us"] = (time.perf_counter() - t0) * 1e6
+    res[f"scale_F{F}_rel_diff_to_reference"] = abs(got - want) / abs(want)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips (default: everything but lpips)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale (default: everything but lpips)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -274,6 +350,10 @@ def main():
         if "lpips" in only:
             for F in (1, 30):
                 out.update(bench_lpips(dev, g, W, H, args.reps, F))
+                torch.cuda.empty_cache()
+        if "scale" in only:
+            for F in (1, 30, 100):
+                out.update(bench_scale(dev, g, W, H, args.reps, F))
                 torch.cuda.empty_cache()
         print(json.dumps({k: (round(v, 2) if v >= 0.01 else float(f"{v:.3g}")) if isinstance(v, float) else v for k, v in out.items()}))
         return
