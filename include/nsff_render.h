@@ -922,6 +922,50 @@ typedef struct NsffFlowMapsArgs {
 int64_t nsff_flow_maps_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
 int nsff_flow_maps(const NsffFlowMapsArgs* args, void* stream);
 
+/* ---- chained scene-flow tracks (csrc/tracks.hip; nsff_pl_amd/tracks.py).  Entry points added without a
+ * change of NSFF_ABI_VERSION: nothing that existed changes.
+ * nsff_track_step: one step of n_rows rows of pts_per_row points each, one launch.  For point p of row r, x = xyz_in[p] (fp32 NDC),
+ * t = t_in[r] (int32), with the records `raw` (n_rows * pts_per_row, NSFF_RAW_STRIDE) of a field query at (x, E_t[t]):
+ *   can = alive_in[r] && (direction > 0 ? t < max_t : t > 0);  f = raw columns 8..10 (direction +1) or 11..13 (-1), set to 0 where
+ *   (x.z + 1f) * 0.5f > 0.95f (the reference's flows[zs > z_far] = 0 on NDC rays);  xyz_out[p] = can ? x + f : x;
+ *   t_out[r] = can ? t + direction : t;  alive_out[r] = can  (uint8 0 / 1; t_out / alive_out must not be t_in / alive_in).
+ * With cameras (Ps, uv and depth given together) the NEW position is projected by Ps[t_out[r]] -- Ps (n_poses, 3, 4), max_t <
+ * n_poses -- or, with fixed_view != 0, by Ps[0]: the chain of nsff_flow_maps' projection (every step one fp32 operation), uv (.., 2)
+ * = (NSFF_FLOW_UNKNOWN, NSFF_FLOW_UNKNOWN) where uvd.z > 0 fails, depth = uvd.z.
+ * raw == NULL (then xyz_out, t_out, alive_out must be NULL and cameras given): nothing moves, xyz_in is projected at t_in -- the
+ * projection of a path's first slab.  raw needs 16-byte, every other array 4-byte alignment (NSFF_ERR_ALIGN); 16-byte accesses are
+ * used where a lane's four points start 16-byte aligned, dwords otherwise.  n_rows * pts_per_row <= NSFF_TRACK_MAX_POINTS. */
+#define NSFF_TRACK_MAX_POINTS 0x7fffffffLL
+typedef struct NsffTrackStepArgs {
+    int64_t n_rows;
+    int32_t pts_per_row, direction, max_t, n_poses, fixed_view, pad_;
+    float   fx, fy, cx, cy;
+    const float* raw;  const float* xyz_in;  const int32_t* t_in;  const uint8_t* alive_in;
+    float* xyz_out;  int32_t* t_out;  uint8_t* alive_out;
+    const float* Ps;  float* uv;  float* depth;
+} NsffTrackStepArgs;
+int nsff_track_step(const NsffTrackStepArgs* args, void* stream);
+
+/* nsff_track_draw: motion trails of n_tracks tracks of n_steps segments on a copy of an (H, W, 3) uint8 image, deterministic.
+ * uv (n_steps + 1, n_tracks, 2) fp32 pixels, ok (n_steps + 1, n_tracks) uint8.  Segment j of track q, uv[j][q] -> uv[j + 1][q], is
+ * drawn when both ends are ok and have |u|, |v| < 32768 (NaN, infinities and NSFF_FLOW_UNKNOWN fail) and, with the ends rounded by
+ * floor(u + 0.5f) to (x0, y0), (x0 + dx, y0 + dy), N = max(|dx|, |dy|) <= H + W.  Its pixels, in integers, i = 0 .. N:
+ *   (x0 + floor((2 i dx + N) / (2 N)), y0 + floor((2 i dy + N) / (2 N)))       (N = 0: the one pixel (x0, y0))
+ * -- N + 1 pixels, both ends included, 8-connected; pixels outside the image are skipped one by one.  A pixel takes the segment with
+ * the largest key ((j + 1) << 20) | q (atomicMax on the uint32 canvas in `scratch`), and out = lut[(255 * (j + 1)) / n_steps]
+ * (lut (256, 3) uint8) there, the image's pixel elsewhere.  n_tracks < NSFF_TRACK_MAX_TRACKS, 1 <= n_steps < NSFF_TRACK_MAX_STEPS
+ * (NSFF_ERR_INVALID).  scratch: nsff_track_draw_scratch_bytes(H, W) bytes, 4-byte aligned, any content; uv 8-byte aligned.
+ * Three launches on `stream`, no synchronisation. */
+#define NSFF_TRACK_MAX_TRACKS (1 << 20)
+#define NSFF_TRACK_MAX_STEPS  (1 << 11)
+typedef struct NsffTrackDrawArgs {
+    int32_t H, W, n_steps, n_tracks;
+    const float* uv;  const uint8_t* ok;  const uint8_t* image;  const uint8_t* lut;  uint8_t* out;
+    void* scratch;  int64_t scratch_bytes;
+} NsffTrackDrawArgs;
+int64_t nsff_track_draw_scratch_bytes(int32_t H, int32_t W);
+int nsff_track_draw(const NsffTrackDrawArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

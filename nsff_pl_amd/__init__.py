@@ -17,6 +17,8 @@ from .frames import (build_records, projection_matrices, resize_images, resize_m
 from .sampling import RayBank
 from . import flow
 from .flow import induced_flow, flow_to_image, flow_epe, epe_from_sums
+from . import tracks
+from .tracks import advect, draw
 from . import panels
 from .panels import validation_panels, error_blend
 from .lpips import LPIPS
@@ -28,5 +30,6 @@ __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "
            "build_records", "projection_matrices", "RayBank",
            "resize_images", "resize_masks", "resize_disps", "resize_flows", "resize_frames", "scaled_intrinsics",
            "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
+           "tracks", "advect", "draw",
            "panels", "validation_panels", "error_blend", "LPIPS",
            "scene", "nearest_depth", "scene_from_colmap", "visibility_matrix"]

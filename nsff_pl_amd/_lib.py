@@ -209,6 +209,22 @@ class FlowMapsArgs(C.Structure):
                 ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+TRACK_MAX_POINTS, TRACK_MAX_TRACKS, TRACK_MAX_STEPS = 0x7fffffff, 1 << 20, 1 << 11      # NSFF_TRACK_MAX_*
+
+
+class TrackStepArgs(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("pts_per_row", C.c_int32), ("direction", C.c_int32), ("max_t", C.c_int32),
+                ("n_poses", C.c_int32), ("fixed_view", C.c_int32), ("pad_", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("raw", _fp), ("xyz_in", _fp), ("t_in", _fp), ("alive_in", _fp), ("xyz_out", _fp), ("t_out", _fp), ("alive_out", _fp),
+                ("Ps", _fp), ("uv", _fp), ("depth", _fp)]
+
+
+class TrackDrawArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("n_steps", C.c_int32), ("n_tracks", C.c_int32),
+                ("uv", _fp), ("ok", _fp), ("image", _fp), ("lut", _fp), ("out", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
 RAY_RECORD = 16
 _DRAW_OUT = ["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
@@ -342,6 +358,9 @@ _SIGNATURES = {
     "nsff_val_panels": (C.c_int, [C.POINTER(ValPanelsArgs), _fp]),
     "nsff_flow_maps_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_flow_maps": (C.c_int, [C.POINTER(FlowMapsArgs), _fp]),
+    "nsff_track_step": (C.c_int, [C.POINTER(TrackStepArgs), _fp]),
+    "nsff_track_draw_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "nsff_track_draw": (C.c_int, [C.POINTER(TrackDrawArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1344,6 +1363,34 @@ def flow_maps(F, H, W, xyz=(None, None), K4=None, Ps=None, ts=None, max_t=0, flo
         a.scratch_bytes = scratch.numel()
     with torch.cuda.device(dev):
         _check(load().nsff_flow_maps(C.byref(a), _stream()), "nsff_flow_maps")
+
+
+def track_step(n_rows, pts_per_row, direction, max_t, xyz_in, t_in, alive_in, raw=None, xyz_out=None, t_out=None, alive_out=None,
+               K4=None, Ps=None, fixed_view=False, uv=None, depth=None):
+    """nsff_track_step: one step of a track chain (raw given), or the projection of its first slab (raw None); one launch."""
+    a = TrackStepArgs()
+    a.n_rows, a.pts_per_row, a.direction, a.max_t = int(n_rows), int(pts_per_row), int(direction), int(max_t)
+    if Ps is not None:
+        a.n_poses, a.fixed_view = int(Ps.shape[0]), int(bool(fixed_view))
+        a.fx, a.fy, a.cx, a.cy = (float(v) for v in K4)
+    a.raw, a.xyz_in, a.xyz_out = _ptr(raw), _ptr(xyz_in), _ptr(xyz_out)
+    a.t_in, a.t_out = _dptr(t_in, torch.int32, "t_in"), _dptr(t_out, torch.int32, "t_out")
+    a.alive_in, a.alive_out = _dptr(alive_in, torch.uint8, "alive_in"), _dptr(alive_out, torch.uint8, "alive_out")
+    a.Ps, a.uv, a.depth = _ptr(Ps), _ptr(uv), _ptr(depth)
+    _check(load().nsff_track_step(C.byref(a), _stream()), "nsff_track_step")
+
+
+def track_draw_scratch_bytes(H, W):
+    return int(load().nsff_track_draw_scratch_bytes(int(H), int(W)))
+
+
+def track_draw(H, W, n_steps, n_tracks, uv, ok, image, lut, out, scratch):
+    """nsff_track_draw: the trails of n_tracks tracks of n_steps segments on a copy of `image`; three launches."""
+    a = TrackDrawArgs(H=int(H), W=int(W), n_steps=int(n_steps), n_tracks=int(n_tracks))
+    a.uv, a.ok = _ptr(uv), _dptr(ok, torch.uint8, "ok")
+    a.image, a.lut, a.out = _dptr(image, torch.uint8, "image"), _dptr(lut, torch.uint8, "lut"), _dptr(out, torch.uint8, "out")
+    a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "scratch"), int(scratch.numel())
+    _check(load().nsff_track_draw(C.byref(a), _stream()), "nsff_track_draw")
 
 
 def cdf(weights, out):

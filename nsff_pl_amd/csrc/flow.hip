@@ -5,7 +5,8 @@
 // nsff_flow_maps, up to two launches:
 //
 // flow_map_kernel -- per pixel and direction
-//   projection   the geometric loss's own chain (losses.py:99-116), one fp32 rounding per operation (built -ffp-contract=off):
+//   projection   the geometric loss's own chain (losses.py:99-116), one fp32 rounding per operation (built -ffp-contract=off;
+//                ndc_to_pixel of nsff_frame_ops.h, which nsff_track_step of tracks.hip calls too):
 //                  world  Rz = 2 / ((z - 1) - 1e-6f), Rx = (((-Rz) * x) * cx) / fx, Ry = (((-Rz) * y) * cy) / fy   (ray_utils.py:142-145)
 //                  uvd_r  = ((P[r][0] * Rx + P[r][1] * Ry) + P[r][2] * Rz) + P[r][3],  P = Ps[min(t + 1, max_t)] (fw), Ps[max(t - 1, 0)] (bw)
 //                  uv     = uvd.xy / (|uvd.z| + 1e-8f),  flow = uv - (px, py)
@@ -105,17 +106,10 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_map_kernel(NsffFlowMapsArgs
             float u, v;
             if (a.xyz[d]) {
                 const float x = s_xyz[d][3 * q], y = s_xyz[d][3 * q + 1], z = s_xyz[d][3 * q + 2];
-                const float Rz = 2.f / ((z - 1.f) - 1e-6f);
-                const float Rx = (((-Rz) * x) * a.cx) / a.fx;
-                const float Ry = (((-Rz) * y) * a.cy) / a.fy;
-                const float* M = P[d];
-                const float ud = ((M[0] * Rx + M[1] * Ry) + M[2] * Rz) + M[3];
-                const float vd = ((M[4] * Rx + M[5] * Ry) + M[6] * Rz) + M[7];
-                const float wd = ((M[8] * Rx + M[9] * Ry) + M[10] * Rz) + M[11];
-                const float den = fabsf(wd) + 1e-8f;
+                const float wd = ndc_to_pixel(x, y, z, P[d], a.fx, a.fy, a.cx, a.cy, u, v);
                 const int py = (int)(p / a.W), px = (int)(p - (int64_t)py * a.W);
-                u = ud / den - (float)px;
-                v = vd / den - (float)py;
+                u = u - (float)px;
+                v = v - (float)py;
                 if (!(wd > 0.f && t_ok[d])) { u = NSFF_FLOW_UNKNOWN; v = NSFF_FLOW_UNKNOWN; }
                 F2[p] = make_float2(u, v);
             } else {

@@ -163,6 +163,25 @@ __device__ __forceinline__ void store_bytes(uint8_t* dst, const uint32_t (&b)[NB
     }
 }
 
+// An NDC point seen by the camera M (3, 4 row-major, world -> pixel): the geometric loss's chain (losses.py:99-116), every step one
+// fp32 operation in a translation unit built -ffp-contract=off (flow.hip, tracks.hip):
+//   world  Rz = 2 / ((z - 1) - 1e-6f), Rx = (((-Rz) * x) * cx) / fx, Ry = (((-Rz) * y) * cy) / fy               (ray_utils.py:142-145)
+//   uvd_r  = ((M[r][0] * Rx + M[r][1] * Ry) + M[r][2] * Rz) + M[r][3],  u = uvd.x / (|uvd.z| + 1e-8f), v likewise
+// Returns uvd.z: the point is in front of the camera when it is > 0 (a NaN point fails that comparison).
+__device__ __forceinline__ float ndc_to_pixel(float x, float y, float z, const float* M, float fx, float fy, float cx, float cy,
+                                              float& u, float& v) {
+    const float Rz = 2.f / ((z - 1.f) - 1e-6f);
+    const float Rx = (((-Rz) * x) * cx) / fx;
+    const float Ry = (((-Rz) * y) * cy) / fy;
+    const float ud = ((M[0] * Rx + M[1] * Ry) + M[2] * Rz) + M[3];
+    const float vd = ((M[4] * Rx + M[5] * Ry) + M[6] * Rz) + M[7];
+    const float wd = ((M[8] * Rx + M[9] * Ry) + M[10] * Rz) + M[11];
+    const float den = fabsf(wd) + 1e-8f;
+    u = ud / den;
+    v = vd / den;
+    return wd;
+}
+
 // np.nan_to_num of an fp32 value: NaN -> 0, +-inf -> +-FLT_MAX
 __device__ __forceinline__ float nan_to_num(float x) { return x != x ? 0.f : fminf(fmaxf(x, -FLT_MAX), FLT_MAX); }
 // torch.clip(x, 0, 1): a NaN stays a NaN

@@ -22,6 +22,8 @@ and PSNR -- the renderer-side pieces of the reference's ``eval.py`` / ``datasets
                            its LPIPS row when given an :class:`nsff_pl_amd.lpips.LPIPS` (eval.py:176-178, 235, 240).
 * :func:`flow_frames`, :class:`FlowScores` -- the flow panel of the reference's test.ipynb: the induced optical flow of every
                            training pose, its colour image beside the dataset's flow, and the end-point error (``nsff_flow_maps``).
+* :func:`track_panel`   -- a frame with the motion trails of its dynamic surface: chained scene-flow tracks both ways in time
+                           (:mod:`nsff_pl_amd.tracks`: ``nsff_track_step``, ``nsff_track_draw``).
 """
 import os
 
@@ -655,6 +657,53 @@ def _flow_frames(models, embeddings, K, poses, img_wh, N_samples, N_importance, 
         pending = (names[i], host)
     if pending is not None:
         yield land(pending)
+
+
+@torch.no_grad()
+def track_panel(models, embeddings, K, poses, t0, img_wh, N_samples, N_importance, steps, stride=16, min_alpha=0.5, lut=None,
+                chunk=1024 * 32, **kwargs):
+    """Frame ``t0`` with the motion trails of its dynamic surface: ``(rgb_u8 (h, w, 3) uint8, tracks)``, all on the GPU.
+
+    K (3,3), poses (N,3,4) the dataset's poses (max_t = N - 1).  Frame t0 is rendered at its own pose; the expected surface point
+    ``xyz_fine`` of every ``stride``-th pixel of every ``stride``-th row whose ``transient_alpha_fine >= min_alpha`` is followed
+    ``steps`` frames forward and ``steps`` frames backward through the scene-flow field (:func:`nsff_pl_amd.tracks.advect`), every step
+    is projected with the fixed camera of pose t0, and both families of trails are drawn on the finished 8-bit frame
+    (:func:`nsff_pl_amd.metrics.finish_frames`, :func:`nsff_pl_amd.tracks.draw`; lut: its (256, 3) colour table), the backward family
+    last.  ``tracks = {'fw', 'bw'}`` (advect's dicts over ALL the strided pixels, one point a row), ``'pixels'`` (Q,) their flat pixel
+    indices and ``'selected'`` (Q,) bool, which of them passed min_alpha: only those are drawn -- nothing here waits for the GPU to
+    learn how many there are."""
+    from . import frames as nframes
+    from . import metrics, tracks
+    model = models['fine']
+    if not getattr(model, "has_flow_heads", False):
+        raise RuntimeError("track_panel: models['fine'] has no scene-flow heads (NeRF(..., encode_transient=True, output_flow=True)): "
+                           "there is no flow to follow")
+    n = len(poses)
+    t0, steps, stride = int(t0), int(steps), int(stride)
+    if not 0 <= t0 < n:
+        raise ValueError(f"track_panel: t0 = {t0} is outside the sequence of {n} poses")
+    if steps < 1 or stride < 1:
+        raise ValueError(f"track_panel: steps and stride must be positive, got {steps} and {stride}")
+    w, h = (int(v) for v in img_wh)
+    device = next(model.parameters()).device
+    K = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)
+    view = nframes.projection_matrices(K, poses)[1][0][t0].to(device).contiguous()
+    rays = frame_rays(torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(np.asarray(poses[t0]), dtype=torch.float32), h, w,
+                      device=device)
+    ts = torch.full((h * w,), t0, dtype=torch.long, device=device)
+    res = render_frame(models, embeddings, rays, ts, n - 1, N_samples, N_importance, chunk,
+                       keys=('rgb_fine', 'xyz_fine', 'transient_alpha_fine'),
+                       **dict(kwargs, output_transient=True, output_transient_flow=['fw', 'bw']))
+    image = metrics.finish_frames(res['rgb_fine'].view(1, h, w, 3))['rgb_u8'][0]
+    ys, xs = torch.meshgrid(torch.arange(0, h, stride, device=device), torch.arange(0, w, stride, device=device), indexing="ij")
+    pixels = (ys * w + xs).reshape(-1)
+    selected = res['transient_alpha_fine'][pixels] >= min_alpha
+    points = res['xyz_fine'][pixels].contiguous()
+    out = {'pixels': pixels, 'selected': selected}
+    for key, k in (('fw', steps), ('bw', -steps)):
+        out[key] = tracks.advect(model, embeddings, points, ts[pixels], k, n - 1, Ps=view, K=K)
+        image = tracks.draw(image, out[key]['uv'], out[key]['alive'] & selected, lut)
+    return image, out
 
 
 def _mask_u8(mask):

@@ -30,6 +30,13 @@ once, the map) over the HBM peak; `act_MB` is what the call actually writes and 
 The scene scale (--only scale) on 1, 30 and 100 frames of 512 x 288 disparities with 20 000 COLMAP points (csrc/scale.hip):
 nsff_scene_scale alone on preallocated outputs and workspace against the byte bound of each of its kernels (bench_scale states the
 arithmetic), the whole scene.nearest_depth call by the host clock, and the reference's per-frame numpy loop, restated in host_numpy_scale, on the same data on the host.
+Scene-flow tracks (--only tracks; csrc/tracks.hip): tracks.advect for n = 8 steps at (R, S) = (147456, 1) -- a 512 x 288 frame of surface
+points -- and (4096, 128), with the fixed-view projection; nsff_track_step alone on preallocated slabs, with and without cameras,
+against the bytes it must move per point (12 B position in, the 12 B of flow, 12 B position out; with cameras 8 + 4 B more) and
+against the bytes it touches when every 64-byte record comes in whole (`rec_bound`) -- also at (131072, 128), 16.8 M points on
+random records, where the launch is long enough for its traffic to show; the field query of one step alone, and the
+step kernel's share of field query + step; nsff_track_draw (three launches) for 10 000 tracks of 8 segments on the frame, against
+clearing, reading and resolving the canvas and the image (4 + 4 + 3 + 3 B per pixel) plus the 8 + 1 B per track end.
 """
 import argparse
 import json
@@ -322,10 +329,58 @@ def bench_scale(dev, g, W, H, reps, F, N=20000):
     return res
 
 
+def bench_tracks(dev, g, W, H, reps, n=8):
+    from nsff_pl_amd import NeRF, PosEmbedding, tracks
+    torch.manual_seed(0)
+    emb = {"xyz": PosEmbedding(9, 10), "t": torch.nn.Embedding(30, 48).to(dev)}
+    model = NeRF("fine", use_viewdir=False, encode_transient=True, in_channels_t=48, output_flow=True).to(dev)
+    K = np.array([[400.0, 0, W / 2], [0, 400.0, H / 2], [0, 0, 1]])
+    view = torch.tensor([[400.0, 0, -W / 2, 0.1], [0, -400.0, -H / 2, 0.05], [0, 0, -1.0, 0.02]], device=dev)
+    freqs = [float(f) for f in emb["xyz"].freqs]
+    res = {}
+    for R, S in ((W * H, 1), (4096, 128), (131072, 128)):       # (the last: the step kernel alone, large enough to time its traffic)
+        P, tag = R * S, f"R{R}_S{S}"
+        big = P > 1 << 22
+        xyz = torch.cat([torch.rand(R, S, 2, device=dev, generator=g) * 2 - 1, torch.rand(R, S, 1, device=dev, generator=g) * 1.85 - 1], -1)
+        ts = torch.randint(0, 20, (R,), device=dev, generator=g, dtype=torch.int32)
+        if not big:
+            res[f"advect_{tag}_n{n}_us"] = time_us(lambda: tracks.advect(model, emb, xyz, ts, n, 29, Ps=view, K=K), max(reps // 5, 3), warmup=2)
+        raw, nxt = torch.empty(P, _lib.RAW_STRIDE, device=dev), torch.empty_like(xyz)
+        alive, t_out, a_out = torch.ones(R, dtype=torch.uint8, device=dev), torch.empty_like(ts), torch.empty(R, dtype=torch.uint8, device=dev)
+        uv, depth = torch.empty(R, S, 2, device=dev), torch.empty(R, S, device=dev)
+        rows = emb["t"](ts.long()).contiguous()
+        query = lambda: _lib.field_query(model, raw, P, S, static_mode=0, transient_mode=2, flow_heads=1, xyz=xyz, freqs=freqs, t_emb=rows)
+        if big:
+            raw.normal_(generator=g)
+            query = lambda: None
+        step = lambda **cam: _lib.track_step(R, S, 1, 29, xyz, ts, alive, raw=raw, xyz_out=nxt, t_out=t_out, alive_out=a_out, **cam)
+        t_query = float("nan") if big else time_us(query, reps)
+        t_step = time_us(step, reps)
+        t_cam = time_us(lambda: step(K4=(400.0, 400.0, W / 2, H / 2), Ps=view[None], fixed_view=True, uv=uv, depth=depth), reps)
+        res.update({f"field_query_{tag}_us": t_query, f"track_step_{tag}_us": t_step, f"track_step_{tag}_bound_us": P * 36 / HBM_PEAK * 1e6,
+                    f"track_step_{tag}_rec_bound_us": P * (24 + 64) / HBM_PEAK * 1e6, f"track_step_cam_{tag}_us": t_cam,
+                    f"track_step_cam_{tag}_bound_us": P * 48 / HBM_PEAK * 1e6, f"track_step_cam_{tag}_rec_bound_us": P * (36 + 64) / HBM_PEAK * 1e6,
+                    f"track_step_cam_{tag}_share_of_step": t_cam / (t_cam + t_query)})
+        del raw, nxt, uv, depth, xyz
+        torch.cuda.empty_cache()
+    Q = 10000
+    walk = torch.cat([torch.rand(1, Q, 2, device=dev, generator=g) * torch.tensor([W, H], device=dev),
+                      torch.randn(n, Q, 2, device=dev, generator=g) * 3], 0).cumsum(0).contiguous()
+    ok = torch.rand(n + 1, Q, device=dev, generator=g) < 0.95
+    image = torch.randint(0, 256, (H, W, 3), device=dev, generator=g, dtype=torch.uint8)
+    lut, out = torch.as_tensor(tracks.default_lut()).to(dev), torch.empty_like(image)
+    scratch = torch.empty(_lib.track_draw_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
+    okb = ok.view(torch.uint8)
+    res[f"track_draw_Q{Q}_n{n}_us"] = time_us(lambda: _lib.track_draw(H, W, n, Q, walk, okb, image, lut, out, scratch), reps)
+    res[f"track_draw_Q{Q}_n{n}_bound_us"] = (H * W * (4 + 4 + 3 + 3) + (n + 1) * Q * 9) / HBM_PEAK * 1e6
+    res[f"tracks_draw_Q{Q}_n{n}_call_us"] = time_us(lambda: tracks.draw(image, walk, ok, lut), reps)
+    return {k: v for k, v in res.items() if v == v}            # (the large case has no field query: its NaN entries are dropped)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale (default: everything but lpips)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks (default: everything but lpips)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -355,6 +410,8 @@ def main():
             for F in (1, 30, 100):
                 out.update(bench_scale(dev, g, W, H, args.reps, F))
                 torch.cuda.empty_cache()
+        if "tracks" in only:
+            out.update(bench_tracks(dev, g, W, H, args.reps))
         print(json.dumps({k: (round(v, 2) if v >= 0.01 else float(f"{v:.3g}")) if isinstance(v, float) else v for k, v in out.items()}))
         return
     gt = torch.rand(H, W, 3, device=dev, generator=g)
