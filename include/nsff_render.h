@@ -966,6 +966,66 @@ typedef struct NsffTrackDrawArgs {
 int64_t nsff_track_draw_scratch_bytes(int32_t H, int32_t W);
 int nsff_track_draw(const NsffTrackDrawArgs* args, void* stream);
 
+/* ---- motion masks from optical flow and camera poses (csrc/motion.hip; nsff_pl_amd/motion.py).  Entry
+ * points added without a change of NSFF_ABI_VERSION: nothing that existed changes.
+ * nsff_motion_maps: one launch for n_frames frames of H x W pixels and both directions (index 0 forward, 1 backward).  Frame f,
+ * direction d uses the neighbour n = f + 1 (fw) / f - 1 (bw), A = flow_fw[f], B = flow_bw[n] (fw) / A = flow_bw[f], B = flow_fw[n]
+ * (bw) -- flow_fw / flow_bw (F, H*W, 2) fp32 pixels -- and M = Fm[f][d], Fm (F, 2, 3, 3) fp32, which maps a pixel of f to its
+ * epipolar line in n.  A frame has no neighbour outside 0 .. F-1.  At the pixel (x, y), integers as floats, every step one fp32
+ * operation in the order written (IEEE division and square root):
+ *   a = A[y][x];  known(a): both components |.| <= 1e7 and not NaN (the Middlebury convention of nsff_flow_maps)
+ *   qx = x + a.u, qy = y + a.v;  inside = 0 <= qx <= W-1 && 0 <= qy <= H-1
+ *   b = B sampled bilinearly at q:  x0 = floorf(qx), ax = qx - x0, x1 = min(x0 + 1, W-1), y likewise, per component
+ *       b = ((B00 * (1 - ax) + B01 * ax) * (1 - ay)) + ((B10 * (1 - ax) + B11 * ax) * ay),  Bij = B[yi][xj];  all four taps known
+ *   s = a + b;  lhs = s.u * s.u + s.v * s.v;  rhs = alpha * ((a.u * a.u + a.v * a.v) + (b.u * b.u + b.v * b.v)) + beta
+ *   consistent = lhs <= rhs                                               (the forward-backward check)
+ *   l_i = (M[i][0] * x + M[i][1] * y) + M[i][2];  r = (l0 * qx + l1 * qy) + l2;  n = l0 * l0 + l1 * l1
+ *   e = fabsf(r) / sqrtf(n);  line_ok = n is finite and > 0               (the distance of q from the epipolar line of (x, y))
+ * Outputs, each optional (at least one):
+ *   err   (F, 2, H*W) fp32   e where there is a neighbour, known(a) and line_ok, else NSFF_FLOW_UNKNOWN
+ *   valid (F, 2, H*W) uint8  1 where neighbour && known(a) && inside && taps known && consistent && line_ok, else 0
+ *   raw   (F, H*W) uint8     0 (dynamic) where valid && e > threshold in either direction, else 255 (static): the polarity of the
+ *                            reference's masks/ *.png
+ *   counts (F, 5) int64 [valid fw, valid bw, over fw, over bw, dynamic pixels of raw] and err_sums (F, 2) fp64, the sum of e over
+ *   the valid pixels of each direction (fp32 terms added in fp64) -- given together; fixed summation order that depends on H * W
+ *   only: the same bits for a frame alone or in a batch.
+ * epipolar == 0 is the consistency check alone: Fm is not read, line_ok counts as true in `valid`, err is NSFF_FLOW_UNKNOWN
+ * everywhere, nothing is over and raw is 255.
+ * No synchronisation, no allocation: capturable.  counts / err_sums are combined from per-workgroup partials in `scratch`:
+ * nsff_motion_maps_scratch_bytes() bytes, 16-byte aligned, ZERO before its first use (every call leaves it as it needs it: the
+ * counter words zero; one call at a time per scratch buffer).  The same size serves nsff_mask_erode.
+ * n_frames <= 65535, 1 <= H * W < 2^31; epipolar not 0 / 1, alpha, beta or threshold negative or NaN, no output, counts without
+ * err_sums or a scratch that is too small: NSFF_ERR_INVALID; a missing flow, Fm (epipolar) or scratch (counts): NSFF_ERR_NULL; flows,
+ * counts and err_sums 8-byte, scratch 16-byte, Fm and err 4-byte aligned (NSFF_ERR_ALIGN) -- all before the launch.  16-byte
+ * accesses are used where every fp32 array is 16-byte and every uint8 array 4-byte aligned and a lane's four pixels start
+ * there, single elements otherwise. */
+typedef struct NsffMotionMapsArgs {
+    int32_t n_frames, H, W, epipolar;
+    float   alpha, beta, threshold, pad_;
+    const float* flow_fw;  const float* flow_bw;  const float* Fm;
+    float* err;  uint8_t* valid;  uint8_t* raw;
+    int64_t* counts;  double* err_sums;
+    void* scratch;  int64_t scratch_bytes;
+} NsffMotionMapsArgs;
+int64_t nsff_motion_maps_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int nsff_motion_maps(const NsffMotionMapsArgs* args, void* stream);
+
+/* nsff_mask_erode: cv2.erode(src, ones((k, k))) of n_frames uint8 images of H x W pixels (any values), one launch:
+ * dst[y][x] = the minimum of src over the k x k window centred on (x, y); pixels outside the image do not contribute (OpenCV's
+ * default border for morphology), so an image smaller than the window is legal.  k odd, 1 .. NSFF_ERODE_MAX_K; k = 1 copies.
+ * zero_counts (F) int64, optional: the number of zero pixels of each frame of dst; it needs `scratch`
+ * (nsff_motion_maps_scratch_bytes() bytes, 16-byte aligned, zero before its first use, left so).  dst must not overlap src.
+ * An even or out-of-range k, dst == src or a scratch that is too small: NSFF_ERR_INVALID; a missing src / dst or scratch
+ * (zero_counts): NSFF_ERR_NULL; zero_counts 8-byte, scratch 16-byte aligned (NSFF_ERR_ALIGN) -- all before the launch.  No
+ * synchronisation, no allocation. */
+#define NSFF_ERODE_MAX_K 31
+typedef struct NsffMaskErodeArgs {
+    int32_t n_frames, H, W, k;
+    const uint8_t* src;  uint8_t* dst;  int64_t* zero_counts;
+    void* scratch;  int64_t scratch_bytes;
+} NsffMaskErodeArgs;
+int nsff_mask_erode(const NsffMaskErodeArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

@@ -19,6 +19,8 @@ from . import flow
 from .flow import induced_flow, flow_to_image, flow_epe, epe_from_sums
 from . import tracks
 from .tracks import advect, draw
+from . import motion
+from .motion import motion_masks, flow_consistency, fundamental_matrices
 from . import panels
 from .panels import validation_panels, error_blend
 from .lpips import LPIPS
@@ -31,5 +33,6 @@ __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "
            "resize_images", "resize_masks", "resize_disps", "resize_flows", "resize_frames", "scaled_intrinsics",
            "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
            "tracks", "advect", "draw",
+           "motion", "motion_masks", "flow_consistency", "fundamental_matrices",
            "panels", "validation_panels", "error_blend", "LPIPS",
            "scene", "nearest_depth", "scene_from_colmap", "visibility_matrix"]

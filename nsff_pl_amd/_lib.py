@@ -225,6 +225,21 @@ class TrackDrawArgs(C.Structure):
                 ("uv", _fp), ("ok", _fp), ("image", _fp), ("lut", _fp), ("out", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+ERODE_MAX_K = 31              # NSFF_ERODE_MAX_K
+
+
+class MotionMapsArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("epipolar", C.c_int32),
+                ("alpha", C.c_float), ("beta", C.c_float), ("threshold", C.c_float), ("pad_", C.c_float),
+                ("flow_fw", _fp), ("flow_bw", _fp), ("Fm", _fp), ("err", _fp), ("valid", _fp), ("raw", _fp),
+                ("counts", _fp), ("err_sums", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
+class MaskErodeArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("k", C.c_int32),
+                ("src", _fp), ("dst", _fp), ("zero_counts", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
 RAY_RECORD = 16
 _DRAW_OUT = ["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
@@ -361,6 +376,9 @@ _SIGNATURES = {
     "nsff_track_step": (C.c_int, [C.POINTER(TrackStepArgs), _fp]),
     "nsff_track_draw_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "nsff_track_draw": (C.c_int, [C.POINTER(TrackDrawArgs), _fp]),
+    "nsff_motion_maps_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_motion_maps": (C.c_int, [C.POINTER(MotionMapsArgs), _fp]),
+    "nsff_mask_erode": (C.c_int, [C.POINTER(MaskErodeArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1391,6 +1409,56 @@ def track_draw(H, W, n_steps, n_tracks, uv, ok, image, lut, out, scratch):
     a.image, a.lut, a.out = _dptr(image, torch.uint8, "image"), _dptr(lut, torch.uint8, "lut"), _dptr(out, torch.uint8, "out")
     a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "scratch"), int(scratch.numel())
     _check(load().nsff_track_draw(C.byref(a), _stream()), "nsff_track_draw")
+
+
+def motion_maps_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_motion_maps_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def motion_maps(flows_fw, flows_bw, Fm=None, alpha=0.01, beta=0.5, threshold=1.0, err=None, valid=None, raw=None, counts=None,
+                err_sums=None, scratch=None):
+    """nsff_motion_maps on (F, H, W, 2) fp32 flows: the forward-backward check and, with Fm (F, 2, 3, 3) fp32, the distance from the
+    epipolar line (without Fm: the check alone) -> err (F, 2, H, W) fp32, valid (F, 2, H, W) uint8, raw (F, H, W) uint8 (0 dynamic,
+    255 static), counts (F, 5) int64 [valid fw, valid bw, over fw, over bw, dynamic] with err_sums (F, 2) fp64 -- whichever are
+    given.  scratch: uint8 tensor of motion_maps_scratch_bytes() bytes, zero before its first use (a fresh one when None)."""
+    require_gpu_tensor(flows_fw, "motion_maps: flows_fw")
+    F, H, W = (int(v) for v in flows_fw.shape[:3])
+    n, dev = F * H * W, flows_fw.device
+    a = MotionMapsArgs(n_frames=F, H=H, W=W, epipolar=int(Fm is not None), alpha=float(alpha), beta=float(beta),
+                       threshold=float(threshold))
+    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, n * 2), ("flow_bw", flows_bw, torch.float32, n * 2),
+                                   ("Fm", Fm, torch.float32, F * 18), ("err", err, torch.float32, n * 2),
+                                   ("valid", valid, torch.uint8, n * 2), ("raw", raw, torch.uint8, n),
+                                   ("counts", counts, torch.int64, F * 5), ("err_sums", err_sums, torch.float64, F * 2)):
+        if t is None:
+            continue
+        ptr = _dptr(t, dtype, f"motion_maps: {field}")
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"motion_maps: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        setattr(a, field, ptr)
+    if counts is not None and scratch is None:
+        scratch = torch.zeros(max(motion_maps_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    if scratch is not None:
+        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "motion_maps: scratch"), scratch.numel()
+    with torch.cuda.device(dev):
+        _check(load().nsff_motion_maps(C.byref(a), _stream()), "nsff_motion_maps")
+
+
+def mask_erode(src, dst, k, zero_counts=None, scratch=None):
+    """nsff_mask_erode: dst = cv2.erode(src, ones((k, k))) per frame of (F, H, W) uint8 images; zero_counts (F,) int64: the zero
+    pixels of each eroded frame.  scratch as for motion_maps."""
+    require_gpu_tensor(src, "mask_erode: src")
+    F, H, W = (int(v) for v in src.shape)
+    a = MaskErodeArgs(n_frames=F, H=H, W=W, k=int(k), src=_dptr(src, torch.uint8, "mask_erode: src"),
+                      dst=_dptr(dst, torch.uint8, "mask_erode: dst"), zero_counts=_dptr(zero_counts, torch.int64, "mask_erode: zero_counts"))
+    if dst.numel() != src.numel() or dst.device != src.device or (zero_counts is not None and zero_counts.numel() != F):
+        raise RuntimeError(f"mask_erode: dst / zero_counts do not go with {tuple(src.shape)} images on {src.device}")
+    if zero_counts is not None and scratch is None:
+        scratch = torch.zeros(max(motion_maps_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=src.device)
+    if scratch is not None:
+        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "mask_erode: scratch"), scratch.numel()
+    with torch.cuda.device(src.device):
+        _check(load().nsff_mask_erode(C.byref(a), _stream()), "nsff_mask_erode")
 
 
 def cdf(weights, out):

@@ -37,6 +37,12 @@ against the bytes it touches when every 64-byte record comes in whole (`rec_boun
 random records, where the launch is long enough for its traffic to show; the field query of one step alone, and the
 step kernel's share of field query + step; nsff_track_draw (three launches) for 10 000 tracks of 8 segments on the frame, against
 clearing, reading and resolving the canvas and the image (4 + 4 + 3 + 3 B per pixel) plus the 8 + 1 B per track end.
+Motion masks (--only motion; csrc/motion.hip) on 1 and 30 frames: nsff_motion_maps alone on preallocated outputs with its statistics,
+nsff_mask_erode alone (k = 15, with the zero count), and the whole motion.motion_masks call (host-side fundamental matrices, their
+upload, the allocations and both launches).  Byte bounds: the map pass must read each of the two flows once (8 + 8 B per pixel: a
+frame's forward flow is A of its own forward direction and B of the next frame's backward one) and write err and valid of both
+directions and raw (2 x (4 + 1) + 1 B): 27 B per pixel; as issued, without any reuse, it asks for 2 x (8 + 8) B of flow: 43 B
+(`issued_bound`).  The erosion reads and writes one byte per pixel: 2 B (its halo re-reads come from cache).
 """
 import argparse
 import json
@@ -377,10 +383,38 @@ def bench_tracks(dev, g, W, H, reps, n=8):
     return {k: v for k, v in res.items() if v == v}            # (the large case has no field query: its NaN entries are dropped)
 
 
+MOTION_MAP_BYTES_PER_PIXEL = (8 + 8) + 2 * (4 + 1) + 1
+MOTION_MAP_ISSUED_BYTES_PER_PIXEL = 2 * (8 + 8) + 2 * (4 + 1) + 1
+
+
+def bench_motion(dev, g, W, H, reps, F):
+    from nsff_pl_amd import motion
+    K = np.array([[400.0, 0, W / 2], [0, 400.0, H / 2], [0, 0, 1]])
+    poses = np.tile(np.eye(4)[:3], (F, 1, 1))
+    poses[:, 0, 3] = 0.1 * np.arange(F)
+    fw = 3 * torch.randn(F, H, W, 2, device=dev, generator=g)
+    bw = -fw + 0.3 * torch.randn(F, H, W, 2, device=dev, generator=g)     # roughly consistent: most pixels take the whole path
+    Fm = motion.fundamental_matrices(K, poses).to(dev)
+    out = dict(err=torch.empty(F, 2, H, W, device=dev), valid=torch.empty(F, 2, H, W, dtype=torch.uint8, device=dev),
+               raw=torch.empty(F, H, W, dtype=torch.uint8, device=dev), counts=torch.empty(F, 5, dtype=torch.int64, device=dev),
+               err_sums=torch.empty(F, 2, dtype=torch.float64, device=dev))
+    mask, zeros = torch.empty(F, H, W, dtype=torch.uint8, device=dev), torch.empty(F, dtype=torch.int64, device=dev)
+    scratch = torch.zeros(_lib.motion_maps_scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    maps = lambda: _lib.motion_maps(fw, bw, Fm, scratch=scratch, **out)
+    erode = lambda: _lib.mask_erode(out["raw"], mask, 15, zero_counts=zeros, scratch=scratch)
+    px = F * H * W
+    return {f"motion_maps_F{F}_us": time_us(maps, reps),
+            f"motion_maps_F{F}_bound_us": px * MOTION_MAP_BYTES_PER_PIXEL / HBM_PEAK * 1e6,
+            f"motion_maps_F{F}_issued_bound_us": px * MOTION_MAP_ISSUED_BYTES_PER_PIXEL / HBM_PEAK * 1e6,
+            f"mask_erode_k15_F{F}_us": time_us(erode, reps),
+            f"mask_erode_k15_F{F}_bound_us": px * 2 / HBM_PEAK * 1e6,
+            f"motion_masks_F{F}_call_us": time_us(lambda: motion.motion_masks(fw, bw, K, poses), reps)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks (default: everything but lpips)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion (default: everything but lpips)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -412,6 +446,9 @@ def main():
                 torch.cuda.empty_cache()
         if "tracks" in only:
             out.update(bench_tracks(dev, g, W, H, args.reps))
+        if "motion" in only:
+            for F in (1, 30):
+                out.update(bench_motion(dev, g, W, H, args.reps, F))
         print(json.dumps({k: (round(v, 2) if v >= 0.01 else float(f"{v:.3g}")) if isinstance(v, float) else v for k, v in out.items()}))
         return
     gt = torch.rand(H, W, 3, device=dev, generator=g)
