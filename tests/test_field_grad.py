@@ -403,3 +403,174 @@ def test_fold_gradient_kernels_match_the_torch_algebra(viewdir, hip_lib):
             continue
         err = (plist[i].grad.double() - r).abs().max().item() / max(r.abs().max().item(), 1e-30)
         assert err < 2e-6, (names[id(plist[i])], err)
+
+
+# ---- ragged point counts through the real kernels ----------------------------------------------------------------------------
+# A launch of P points, P no multiple of 64, feeds every weight-gradient GEMM and the data-gradient chain a last tile with
+# 64 "points" of which only P % 64 exist.  The same launch PADDED to P' = 64 ceil(P / 64) points -- the same first P points, time
+# rows and cotangent rows, the added rows with ZERO cotangent (all 16 record floats) -- has the same tile count, hence the same
+# kernel choice, split plan and gmax, and its added points contribute exact zeros to every sum: the two runs must agree BIT FOR BIT
+# in every parameter gradient and in the first P rows of d_xyz / first P / s rows of d_t.  A tail lane that contributes, or an
+# unwritten tail of a saved tile that reaches a product, breaks that.  test_padded_run_matches_float64 anchors the chain
+# "ragged = padded = float64".
+# (P, points per ray, forward tile setting): 1, 2, 3 and 5 tiles of 64 -- an even count runs the hand-scheduled data-gradient
+# kernel, an odd one the compiler-scheduled one --, tails of 1, 63 and 59 points, rays that straddle the last tile
+RAGGED = [(1, 1, 64), (63, 1, 64), (65, 1, 130), (127, 1, 64), (129, 1, 130), (191, 1, 64), (129, 3, 64), (315, 5, 130)]
+
+
+def _ragged_inputs(P, s, seed=23):
+    """the PADDED inputs (the ragged run takes their first P points / P // s rays): xyz (P', 3), t_rows (P' / s, N_TAU), cot (P', 16)"""
+    dev = torch.device("cuda:0")
+    Pp = (P + 63) // 64 * 64
+    assert P % s == 0 and Pp % s == 0 and Pp > P
+    g = torch.Generator().manual_seed(seed + P)
+    xyz = torch.rand(Pp, 3, generator=g) * 2 - 1
+    t_rows = torch.randn(Pp // s, scenes.N_TAU, generator=g)
+    cot = torch.randn(Pp, 16, generator=g)
+    cot[P:] = 0.0                                       # the added points: no cotangent, the unused record floats included
+    return xyz.to(dev), t_rows.to(dev), cot.to(dev)
+
+
+def _run_node(model, freqs, xyz, t_rows, cot, s, static, tile, deferred):
+    """one forward + backward of the field node -> (raw, {parameter: gradient or None}, d_xyz or None, d_t, data-gradient kernel)"""
+    from nsff_pl_amd import _lib
+    x = xyz.detach().clone().requires_grad_(not static)
+    t = t_rows.detach().clone().requires_grad_(True)
+    for p in model.parameters():
+        p.grad = torch.zeros_like(p) if deferred else None      # (deferred: every .grad in place -> nsff_weight_grad_accumulate)
+    A.config.set_tile_points(tile)
+    try:
+        if deferred:
+            with field_grad.deferred_weight_grads():
+                raw = field_grad.field(model, x, freqs, t, s, static, True)
+                raw.backward(cot)
+        else:
+            raw = field_grad.field(model, x, freqs, t, s, static, True)
+            raw.backward(cot)
+    finally:
+        A.config.set_tile_points(0)
+    torch.cuda.synchronize()
+    assert not field_grad._PENDING
+    grads = {n: None if p.grad is None else p.grad.detach().clone() for n, p in model.named_parameters()}
+    return raw.detach(), grads, x.grad, t.grad, _lib.last_bwd_kernel()
+
+
+def _bits_differ(a, b):
+    """None when a and b are the same bits, else a description of how they differ"""
+    a, b = a.contiguous(), b.contiguous()
+    if a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32)):
+        return None
+    if a.shape != b.shape:
+        return f"shapes {tuple(a.shape)} / {tuple(b.shape)}"
+    d = (a.double() - b.double()).abs()
+    return (f"{int((a.view(torch.int32) != b.view(torch.int32)).sum())} of {a.numel()} words differ, {int((a != b).sum())} in value; "
+            f"largest difference {float(d.nan_to_num(float('inf')).max()):.3e} at a largest element of {float(b.abs().max()):.3e}; "
+            f"NaNs {int(a.isnan().sum())} / {int(b.isnan().sum())}")
+
+
+@pytest.mark.parametrize("deferred", [True, False], ids=["in_place", "overlap_0"])
+@pytest.mark.parametrize("static", [True, False], ids=["both_trunks", "dynamic_only"])
+@pytest.mark.parametrize("P,s,tile", RAGGED)
+def test_ragged_launch_equals_its_zero_padded_twin(P, s, tile, static, deferred, hip_lib, grad_precision, monkeypatch):
+    """(see the comment above RAGGED)  deferred: the default of the trainer, the split-K partials accumulated straight into .grad;
+    otherwise NSFF_WGRAD_OVERLAP=0, the gradients returned through autograd (nsff_wgrad_reduce_kernel)."""
+    dev = torch.device("cuda:0")
+    if deferred:
+        monkeypatch.delenv("NSFF_WGRAD_OVERLAP", raising=False)
+    else:
+        monkeypatch.setenv("NSFF_WGRAD_OVERLAP", "0")
+    cfg = scenes.CASES["g3_nsff_train"]
+    models, emb = scenes.build_scene(A.NeRF, A.PosEmbedding, cfg)
+    model = models["fine"].to(dev)
+    freqs = [float(f) for f in emb["xyz"].freqs]
+    xyz, t_rows, cot = _ragged_inputs(P, s)
+    Pp = xyz.shape[0]
+    field_grad._GRAD_MAPS.clear()
+    raw_r, g_r, dx_r, dt_r, k_r = _run_node(model, freqs, xyz[:P], t_rows[:P // s], cot[:P], s, static, tile, deferred)
+    raw_p, g_p, dx_p, dt_p, k_p = _run_node(model, freqs, xyz, t_rows, cot, s, static, tile, deferred)
+    assert bool(field_grad._GRAD_MAPS) == deferred                      # the accumulation route that was asked for
+    # which data-gradient kernel ran: three products have their own; else an even tile count the hand-scheduled body
+    tiles = Pp // 64
+    want_kernel = "x3" if grad_precision == "f16x3" else ("h3b" if tiles % 2 == 0 else "c")
+    assert (k_r, k_p) == (want_kernel, want_kernel)
+    # the forward first: the first P records (the floats a launch defines: 0..13) are the same bits
+    assert raw_r.shape == (P, 16) and raw_p.shape == (Pp, 16)
+    assert _bits_differ(raw_r[:, :14], raw_p[:P, :14]) is None, _bits_differ(raw_r[:, :14], raw_p[:P, :14])
+    bad = {}
+    n_grads = 0
+    for n in g_p:
+        if g_p[n] is None or g_r[n] is None:
+            assert g_p[n] is None and g_r[n] is None and n.startswith("static") and not static, n
+            continue
+        n_grads += 1
+        assert bool(g_p[n].isfinite().all()), n
+        why = _bits_differ(g_r[n], g_p[n])
+        if why:
+            bad[n] = why
+    used = [n for n in g_p if g_p[n] is not None and float(g_p[n].abs().max()) > 0]
+    # (the model has 22 static and 26 dynamic parameter tensors: the comparison is not one of empty gradients)
+    assert n_grads == (48 if static or deferred else 26) and len(used) >= (40 if static else 22), (n_grads, used)
+    bad["d_t"] = _bits_differ(dt_r, dt_p[:P // s])
+    if not static:
+        bad["d_xyz"] = _bits_differ(dx_r, dx_p[:P])
+        assert float(dx_p[P:].abs().max()) == 0                          # (a point without cotangent receives no gradient)
+    else:
+        assert dx_r is None and dx_p is None
+    bad = {k: v for k, v in bad.items() if v}
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("static", [True, False], ids=["both_trunks", "dynamic_only"])
+def test_padded_run_matches_float64(static, hip_lib):
+    """The anchor of the chain "ragged = padded = float64": the padded twin of the 127-point launch (P' = 128, one ray per point,
+    zero cotangent on the added point) against float64 autograd, by the rule of test_field_node_gradients unchanged."""
+    dev = torch.device("cuda:0")
+    cfg = scenes.CASES["g3_nsff_train"]
+    models, emb = scenes.build_scene(A.NeRF, A.PosEmbedding, cfg)
+    model = models["fine"].to(dev)
+    freqs = [float(f) for f in emb["xyz"].freqs]
+    xyz, t_rows, cot = _ragged_inputs(127, 1)
+    ref_p, ref_x, ref_t = _reference_grads(model, xyz, t_rows, 1, freqs, cot, static, True)
+    f32_p, f32_x, f32_t = _reference_grads(model, xyz, t_rows, 1, freqs, cot, static, True, torch.float32)
+    _, grads, d_x, d_t, _ = _run_node(model, freqs, xyz, t_rows, cot, 1, static, 64, False)
+
+    def rel(a, b, scale=None):
+        return float((a.double() - b).abs().max() / (scale if scale is not None else b.abs().max()).clamp_min(1e-300))
+    worst, base = {}, {}
+    for n in grads:
+        if ref_p[n].abs().max() == 0:
+            assert grads[n] is None or float(grads[n].abs().max()) == 0, n
+            continue
+        layer = n.rsplit(".", 1)[0]
+        scale = torch.stack([ref_p[layer + ".weight"].abs().max(), ref_p[layer + ".bias"].abs().max()]).max()
+        worst[n], base[n] = rel(grads[n], ref_p[n], scale), rel(f32_p[n], ref_p[n], scale)
+    worst["t"], base["t"] = rel(d_t, ref_t), rel(f32_t, ref_t)
+    if not static:
+        worst["xyz"], base["xyz"] = rel(d_x, ref_x), rel(f32_x, ref_x)
+    tol = 2e-3
+    k = max(worst, key=worst.get)
+    print("\nworst native at 128 points", static, worst[k], k, "fp32 torch there", base[k], "| fp32 torch worst", max(base.values()))
+    bad = {k: (v, base[k]) for k, v in worst.items() if v > tol + 3 * base[k]}
+    assert not bad, bad
+
+
+def test_the_added_points_do_reach_the_sums(hip_lib, grad_precision):
+    """Control of test_ragged_launch_equals_its_zero_padded_twin: the added point of the padded 127-point launch is a real point of
+    the launch -- give it a cotangent and every weight gradient that is not identically zero changes.  (It is its zero cotangent
+    that makes the padded run equal to the ragged one, not a launch that leaves the point out.)"""
+    dev = torch.device("cuda:0")
+    cfg = scenes.CASES["g3_nsff_train"]
+    models, emb = scenes.build_scene(A.NeRF, A.PosEmbedding, cfg)
+    model = models["fine"].to(dev)
+    freqs = [float(f) for f in emb["xyz"].freqs]
+    xyz, t_rows, cot = _ragged_inputs(127, 1)
+    _, g_zero, _, dt_zero, _ = _run_node(model, freqs, xyz, t_rows, cot, 1, True, 64, False)
+    cot2 = cot.clone()
+    cot2[127:, :14] = 0.5                          # (well below the column maxima: gmax and with it every scale stay as they are)
+    assert bool((cot[:, :14].abs().amax(0) > 0.5).all())
+    _, g_one, _, dt_one, _ = _run_node(model, freqs, xyz, t_rows, cot2, 1, True, 64, False)
+    weights = [n for n in g_zero if n.endswith(".weight")]
+    assert len(weights) == 24
+    same = [n for n in weights if _bits_differ(g_zero[n], g_one[n]) is None]
+    assert not same, same
+    assert _bits_differ(dt_zero[:127], dt_one[:127]) is None and float(dt_zero[127].abs().max()) == 0 and float(dt_one[127].abs().max()) > 0
