@@ -737,9 +737,13 @@ typedef struct NsffMpiArgs {
 } NsffMpiArgs;
 int nsff_mpi_composite(const NsffMpiArgs* args, void* stream);
 
-/* ---- N1: backward of nsff_composite for the training configurations (has_rgb = 1, flow_mode 0 or 2): gradients
+/* ---- N1: backward of nsff_composite for the training configurations (has_rgb = 1, flow_mode 0, 1 or 2): gradients
  * w.r.t. the raw records of the main pass and of the two warped re-queries, and w.r.t. the (far-masked) per-sample
- * flows that enter the per-ray flow expectations.  g_* = gradient of the output of that name (NULL = zero):
+ * flows that enter the per-ray flow expectations.  flow_mode (has_transient only, else NSFF_ERR_INVALID): 0 no flow
+ * outputs; 1 the per-ray expectations xyz_exp / flow_fw_exp / flow_bw_exp without the warped renders -- xyz, f_fw, f_bw
+ * are required, d_f_fw / d_f_bw are written where given, raw_fw / raw_bw / noise_fw / noise_bw / g_rgb_fw / g_rgb_bw /
+ * d_raw_fw / d_raw_bw are neither read nor written; 2 also rgb_fw / rgb_bw (raw_fw, raw_bw, d_raw_fw, d_raw_bw required).
+ * tests/test_composite_kernels.py holds all three to float64.  g_* = gradient of the output of that name (NULL = zero):
  * per sample (n_rays, S): static_sigmas, transient_sigmas, static_weights, transient_weights, weights;
  * per ray: depth (n), rgb (n,3), transient_alpha (n), transient_rgb (n,3), so_rgb = _static_rgb (n,3), so_depth =
  * _static_depth (n), xyz_exp = xyz_fine (n,3), flow_fw_exp / flow_bw_exp = transient_flow_fw / _bw (n,3), rgb_fw, rgb_bw.

@@ -7,7 +7,10 @@
 // them back to front: every product chain T_i = prod_{j<i} om_j is differentiated with the exact reverse recurrence
 //      R_j = dT_{j+1} + om_{j+1} R_{j+1},   d om_j = T_j R_j
 // (a suffix scan of affine maps across the wave, carried between chunks) -- no division, so saturated samples
-// (om = 0) need no special case.  Memory-bound: ~250 B per sample.
+// (om = 0) need no special case.  d alpha / d sigma = delta exp(-delta sigma) takes the exponential itself, not 1 - alpha:
+// the difference is quantised to 2^-24, which is percents of exp(-delta sigma) where a sample is nearly opaque (the
+// last sample's delta of 100, a dense sample) -- and that sample is the whole gradient of a ray it hides.
+// Memory-bound: ~250 B per sample.
 #include "nsff_common.h"
 
 namespace {
@@ -56,6 +59,7 @@ __device__ __forceinline__ float rev_affine(float m, float c, float& carry, int 
 struct Fwd {           // forward quantities of one sample, recomputed from the raw records
     float z, d_s, d_t;
     float xs, sig_s, al_s, xt, sig_t, al_t, alpha;
+    float e_s, e_t, e_w[2];                // exp(-delta sigma) of the static, transient and warped transient field
     float rgb_s[3], rgb_t[3];
     float xw[2], al_w[2], rgb_w[2][3];     // warps: 0 = fw, 1 = bw
 };
@@ -68,26 +72,29 @@ __device__ __forceinline__ void load_fwd(Fwd& f, const NsffCompositeBwdArgs& a, 
     const float* rec = a.raw + idx * RS;
     f.xs = rec[3] + (a.noise_static ? a.noise_static[idx] * a.noise_std : 0.f);
     f.sig_s = softplus(f.xs);
-    f.al_s = 1.f - expf(-f.d_s * f.sig_s);
+    f.e_s = expf(-f.d_s * f.sig_s);
+    f.al_s = 1.f - f.e_s;
     f.rgb_s[0] = rec[0]; f.rgb_s[1] = rec[1]; f.rgb_s[2] = rec[2];
-    f.xt = 0.f; f.sig_t = 0.f; f.al_t = 0.f; f.alpha = f.al_s;
+    f.xt = 0.f; f.sig_t = 0.f; f.al_t = 0.f; f.e_t = 1.f; f.alpha = f.al_s;
     f.rgb_t[0] = f.rgb_t[1] = f.rgb_t[2] = 0.f;
     if (tr) {
         f.xt = rec[7] + (a.noise_transient ? a.noise_transient[idx] * a.noise_std : 0.f);
         f.sig_t = softplus(f.xt);
-        f.al_t = 1.f - expf(-f.d_t * f.sig_t);
+        f.e_t = expf(-f.d_t * f.sig_t);
+        f.al_t = 1.f - f.e_t;
         f.alpha = 1.f - (1.f - f.al_s) * (1.f - f.al_t);
         f.rgb_t[0] = rec[4]; f.rgb_t[1] = rec[5]; f.rgb_t[2] = rec[6];
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        f.xw[k] = 0.f; f.al_w[k] = 0.f;
+        f.xw[k] = 0.f; f.al_w[k] = 0.f; f.e_w[k] = 1.f;
         f.rgb_w[k][0] = f.rgb_w[k][1] = f.rgb_w[k][2] = 0.f;
         if (warps) {
             const float* rw = (k == 0 ? a.raw_fw : a.raw_bw) + idx * RS;
             const float* nz = k == 0 ? a.noise_fw : a.noise_bw;
             f.xw[k] = rw[7] + (nz ? nz[idx] * a.noise_std : 0.f);
-            f.al_w[k] = 1.f - expf(-f.d_t * softplus(f.xw[k]));
+            f.e_w[k] = expf(-f.d_t * softplus(f.xw[k]));
+            f.al_w[k] = 1.f - f.e_w[k];
             f.rgb_w[k][0] = rw[4]; f.rgb_w[k][1] = rw[5]; f.rgb_w[k][2] = rw[6];
         }
     }
@@ -239,17 +246,17 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void composite_bwd_kernel(con
                 const float d_al = -Tw[k] * R;                      // al = 1 - (1-al_s)(1-al_w), om_w = 1 - al
                 d_al_s += d_al * (1.f - f.al_w[k]);
                 d_al_w += d_al * (1.f - f.al_s);
-                d_xw[k] = d_al_w * f.d_t * (1.f - f.al_w[k]) * sigmoidf(f.xw[k]);
+                d_xw[k] = d_al_w * f.d_t * f.e_w[k] * sigmoidf(f.xw[k]);
             }
         }
         if (!on) continue;
-        // -- back through alpha = 1 - exp(-delta softplus(x)) --
-        const float d_sig_s = ld(a.g_static_sigmas, idx) + d_al_s * f.d_s * (1.f - f.al_s);
+        // -- back through alpha = 1 - exp(-delta softplus(x)): d alpha / d sigma = delta exp(-delta sigma) --
+        const float d_sig_s = ld(a.g_static_sigmas, idx) + d_al_s * f.d_s * f.e_s;
         float* dr = a.d_raw + idx * RS;
         float4 o0 = make_float4(d_rgb_s[0], d_rgb_s[1], d_rgb_s[2], d_sig_s * sigmoidf(f.xs));
         float4 o1 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (tr) {
-            const float d_sig_t = ld(a.g_transient_sigmas, idx) + d_al_t * f.d_t * (1.f - f.al_t);
+            const float d_sig_t = ld(a.g_transient_sigmas, idx) + d_al_t * f.d_t * f.e_t;
             o1 = make_float4(d_rgb_t[0], d_rgb_t[1], d_rgb_t[2], d_sig_t * sigmoidf(f.xt));
         }
         reinterpret_cast<float4*>(dr)[0] = o0;
