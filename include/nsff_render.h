@@ -1030,6 +1030,82 @@ typedef struct NsffMaskErodeArgs {
 } NsffMaskErodeArgs;
 int nsff_mask_erode(const NsffMaskErodeArgs* args, void* stream);
 
+/* ---- TV-L1 optical flow (csrc/optflow.hip; nsff_pl_amd/optflow.py): dense flow between P image pairs, the
+ * classical stand-in for the reference's RAFT step (preprocess.py:106-120).  Zach, Pock and Bischof 2007 in the fixed-iteration
+ * form of Sanchez, Meinhardt-Llopis and Facciolo (IPOL 2013).  Entry points added without a change of NSFF_ABI_VERSION: nothing that
+ * existed changes.  Every array is fp32 unless said otherwise, every image plane (n, H, W) contiguous, and every step below ONE
+ * fp32 operation in the order written (the file is built -ffp-contract=off; IEEE division and square root), which the tests
+ * compare bit for bit with numpy.  No atomics, no reductions, no synchronisation, no allocation: every call is capturable.
+ * Common refusals, all before a launch: a size outside the stated range, a bad flag or a scratch that is too small NSFF_ERR_INVALID;
+ * a missing pointer NSFF_ERR_NULL; an array off its element's alignment NSFF_ERR_ALIGN.
+ *
+ * grey     channels == 3: src (n, H*W, 3) uint8 -> dst = (0.299f * R + 0.587f * G) + 0.114f * B on the 0..255 scale;
+ *          channels == 1: src fp32, copied.
+ * down     one pyramid step, (n, H, W) -> (n, (H+1)/2, (W+1)/2): the separable binomial [1, 4, 6, 4, 1] / 16 with a replicated
+ *          border, horizontal pass first, each pass  (((a[-2] + a[+2]) + (a[-1] + a[+1]) * 4f) + a[0] * 6f) * 0.0625f,  then every
+ *          second pixel from (0, 0).  H, W >= 2.
+ * up       a coarse plane (n, h, w) to the next finer level (n, H, W), (H+1)/2 == h and (W+1)/2 == w: bilinear at
+ *          cx = min(x * 0.5f, w-1), cy likewise -- x0 = floorf(cx), ax = cx - x0, x1 = min(x0 + 1, w-1),
+ *          ((c00 * (1 - ax) + c01 * ax) * (1 - ay)) + ((c10 * (1 - ax) + c11 * ax) * ay) -- and the value times 2f.
+ * median   the 3 x 3 median of every plane with a replicated border; dst must not be src.
+ * warp     per pair and pixel, with (u1, u2) the flow so far: Dx = (I1[y][min(x+1, W-1)] - I1[y][max(x-1, 0)]) * 0.5f, Dy likewise
+ *          along y; I1, Dx and Dy sampled bilinearly (the formula of `up`) at cx = min(max(x + u1, 0), W-1), cy likewise ->
+ *          I1w, Ix, Iy;  g = Ix * Ix + Iy * Iy;  rho_c = ((I1w - Ix * u1) - Iy * u2) - I0.
+ *          consts: five planes of P * H * W values each: Ix | Iy | g | rho_c | I1w.
+ * iterate  `iters` iterations on a state of six planes of P * H * W values each, u1 | u2 | p11 | p12 | p21 | p22, with
+ *          l_t = lambda * theta and taut = tau / theta (fp32, formed on the host):
+ *            rho = (rho_c + Ix * u1) + Iy * u2;  lg = l_t * g
+ *            f = rho < -lg ? l_t : rho > lg ? -l_t : g > 1e-10f ? (-rho) / g : 0
+ *            v1 = u1 + f * Ix;  v2 = u2 + f * Iy
+ *            div1 = dx(p11) + dy(p12),  dx(p)(x) = p(x) in the first column, p(x) - p(x-1) inside, -p(x-1) in the last; dy by rows
+ *            u1' = v1 + theta * div1   (u2' from v2, p21, p22)
+ *            ux = u1'(x+1) - u1'(x), 0 in the last column; uy by rows, 0 in the last row;  ng = sqrtf(ux * ux + uy * uy)
+ *            p11' = (p11 + taut * ux) / (1f + taut * ng);  p12' = (p12 + taut * uy) / (same)   (p21', p22' from u2')
+ *          The iterations go back and forth between state[0] (the input) and state[1]; the result is in
+ *          state[nsff_optflow_result_slot(iters, fused ? k : 1)].  fused == 0: one launch per iteration, the definition.
+ *          fused == 1: k iterations per launch on a tile x tile block of pixels held in LDS with a halo of k pixels, bit-identical
+ *          to the plain route for every iters (a last launch runs iters % k); (tile, k) one of the built pairs, (16, 2), (32, 2),
+ *          (32, 3), (32, 4), (32, 6), or (0, 0) = NSFF_OPTFLOW_TILE, NSFF_OPTFLOW_K, the measured default.
+ *          4 <= H, W; P <= 65535; P * H * W < 2^31; 1 <= iters <= 100000; lambda, theta, tau > 0 and finite.
+ * nsff_optflow: the whole estimate for P pairs, images0[p] -> images1[p]: grey, `levels` pyramid levels (clipped so that the
+ *          coarsest keeps both sides >= 4), and from the coarsest level down: the flow of the level above through `up` (zero at the
+ *          coarsest), the dual variables p zero, then `warps` times { warp; iterate; median when `median` != 0 }.
+ *          flow (P, H*W, 2): pixels, x first.  images: channels == 3 uint8 (P, H*W, 3), channels == 1 fp32 (P, H*W).
+ *          16 <= H, W (NSFF_OPTFLOW_MIN_SIZE); 1 <= levels <= 16, 1 <= warps <= 1000; scratch: nsff_optflow_scratch_bytes bytes (0 = the
+ *          shape is refused), 16-byte aligned, any content. */
+#define NSFF_OPTFLOW_MIN_SIZE 16
+#define NSFF_OPTFLOW_TILE     32   /* the fused route's default tile side ...                                    */
+#define NSFF_OPTFLOW_K        3    /* ... and iterations per launch (DESIGN.md section 11.4 has the measurement) */
+#define NSFF_OPTFLOW_FUSED    1    /* the route nsff_pl_amd.optflow takes when not told: 1 fused, 0 plain        */
+typedef struct NsffOptflowIterArgs {
+    int32_t n_pairs, H, W, iters;
+    int32_t fused, tile, k, pad_;
+    float   lambda, theta, tau, pad1_;
+    const float* consts;  float* state[2];
+} NsffOptflowIterArgs;
+typedef struct NsffOptflowArgs {
+    int32_t n_pairs, H, W, channels;
+    int32_t levels, warps, iters, median;
+    int32_t fused, tile, k, pad_;
+    float   lambda, theta, tau, pad1_;
+    const void* images0;  const void* images1;  float* flow;
+    void* scratch;  int64_t scratch_bytes;
+} NsffOptflowArgs;
+int     nsff_optflow_grey(const void* src, float* dst, int32_t n, int32_t H, int32_t W, int32_t channels, void* stream);
+int     nsff_optflow_down(const float* src, float* dst, int32_t n, int32_t H, int32_t W, void* stream);
+int     nsff_optflow_up(const float* src, float* dst, int32_t n, int32_t H, int32_t W, void* stream);
+int     nsff_optflow_median(const float* src, float* dst, int32_t n, int32_t H, int32_t W, void* stream);
+int     nsff_optflow_warp(const float* I0, const float* I1, const float* u, float* consts, int32_t n_pairs, int32_t H, int32_t W,
+                          void* stream);
+int     nsff_optflow_iterate(const NsffOptflowIterArgs* args, void* stream);
+/* host only: 0 or 1, the state buffer that holds the result of `iters` iterations run k per launch (k = 1: the plain route);
+ * negative for iters < 1 or k < 1 */
+int     nsff_optflow_result_slot(int32_t iters, int32_t k);
+/* host only: the number of pyramid levels nsff_optflow uses for an H x W image when asked for `levels` (0: a refused shape) */
+int     nsff_optflow_levels(int32_t H, int32_t W, int32_t levels);
+int64_t nsff_optflow_scratch_bytes(int32_t n_pairs, int32_t H, int32_t W, int32_t levels);
+int     nsff_optflow(const NsffOptflowArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

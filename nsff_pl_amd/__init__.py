@@ -21,6 +21,8 @@ from . import tracks
 from .tracks import advect, draw
 from . import motion
 from .motion import motion_masks, flow_consistency, fundamental_matrices
+from . import optflow
+from .optflow import optical_flow, sequence_flows
 from . import panels
 from .panels import validation_panels, error_blend
 from .lpips import LPIPS
@@ -34,5 +36,6 @@ __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "
            "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
            "tracks", "advect", "draw",
            "motion", "motion_masks", "flow_consistency", "fundamental_matrices",
+           "optflow", "optical_flow", "sequence_flows",
            "panels", "validation_panels", "error_blend", "LPIPS",
            "scene", "nearest_depth", "scene_from_colmap", "visibility_matrix"]

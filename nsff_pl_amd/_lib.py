@@ -240,6 +240,25 @@ class MaskErodeArgs(C.Structure):
                 ("src", _fp), ("dst", _fp), ("zero_counts", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+OPTFLOW_MIN_SIZE, OPTFLOW_TILE, OPTFLOW_K, OPTFLOW_FUSED = 16, 32, 3, 1       # NSFF_OPTFLOW_*
+OPTFLOW_PAIRS = ((16, 2), (32, 2), (32, 3), (32, 4), (32, 6))                # the (tile, k) the fused iteration is built for
+
+
+class OptflowIterArgs(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("iters", C.c_int32),
+                ("fused", C.c_int32), ("tile", C.c_int32), ("k", C.c_int32), ("pad_", C.c_int32),
+                ("lam", C.c_float), ("theta", C.c_float), ("tau", C.c_float), ("pad1_", C.c_float),
+                ("consts", _fp), ("state", _fp * 2)]
+
+
+class OptflowArgs(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32),
+                ("levels", C.c_int32), ("warps", C.c_int32), ("iters", C.c_int32), ("median", C.c_int32),
+                ("fused", C.c_int32), ("tile", C.c_int32), ("k", C.c_int32), ("pad_", C.c_int32),
+                ("lam", C.c_float), ("theta", C.c_float), ("tau", C.c_float), ("pad1_", C.c_float),
+                ("images0", _fp), ("images1", _fp), ("flow", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
 RAY_RECORD = 16
 _DRAW_OUT = ["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
@@ -379,6 +398,16 @@ _SIGNATURES = {
     "nsff_motion_maps_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_motion_maps": (C.c_int, [C.POINTER(MotionMapsArgs), _fp]),
     "nsff_mask_erode": (C.c_int, [C.POINTER(MaskErodeArgs), _fp]),
+    "nsff_optflow_grey": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "nsff_optflow_down": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "nsff_optflow_up": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "nsff_optflow_median": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "nsff_optflow_warp": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "nsff_optflow_iterate": (C.c_int, [C.POINTER(OptflowIterArgs), _fp]),
+    "nsff_optflow_result_slot": (C.c_int, [C.c_int32, C.c_int32]),
+    "nsff_optflow_levels": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_optflow_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_optflow": (C.c_int, [C.POINTER(OptflowArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1459,6 +1488,122 @@ def mask_erode(src, dst, k, zero_counts=None, scratch=None):
         a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "mask_erode: scratch"), scratch.numel()
     with torch.cuda.device(src.device):
         _check(load().nsff_mask_erode(C.byref(a), _stream()), "nsff_mask_erode")
+
+
+# ---- TV-L1 optical flow (csrc/optflow.hip).  Planes are contiguous fp32 (n, H, W) GPU tensors; the stage calls return their output.
+def _planes(t, what, dtype=torch.float32):
+    _dptr(t, dtype, what)
+    if t.dim() != 3:
+        raise RuntimeError(f"{what}: need (n, H, W) planes, got {tuple(t.shape)}")
+    return tuple(int(v) for v in t.shape)
+
+
+def optflow_grey(src):
+    """nsff_optflow_grey: (n, H, W, 3) uint8 -> (n, H, W) fp32 grey on the 0..255 scale; (n, H, W) fp32 is copied."""
+    channels = 3 if src.dtype == torch.uint8 else 1
+    _dptr(src, torch.uint8 if channels == 3 else torch.float32, "optflow_grey: src")
+    if src.dim() != (4 if channels == 3 else 3) or (channels == 3 and src.shape[-1] != 3):
+        raise RuntimeError(f"optflow_grey: src: need (n, H, W, 3) uint8 or (n, H, W) float32, got {tuple(src.shape)}")
+    n, H, W = (int(v) for v in src.shape[:3])
+    dst = torch.empty(n, H, W, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _check(load().nsff_optflow_grey(src.data_ptr(), dst.data_ptr(), n, H, W, channels, _stream()), "nsff_optflow_grey")
+    return dst
+
+
+def _optflow_planes(name, src, out_hw=None):
+    n, H, W = _planes(src, f"optflow_{name}: src")
+    oh, ow = ((H + 1) // 2, (W + 1) // 2) if name == "down" else (out_hw or (H, W))
+    if name == "up" and ((oh + 1) // 2, (ow + 1) // 2) != (H, W):
+        raise RuntimeError(f"optflow_up: a {H} x {W} level is not the half of {oh} x {ow}")
+    dst = torch.empty(n, oh, ow, dtype=torch.float32, device=src.device)
+    dims = (n, oh, ow) if name == "up" else (n, H, W)
+    with torch.cuda.device(src.device):
+        _check(getattr(load(), f"nsff_optflow_{name}")(src.data_ptr(), dst.data_ptr(), *dims, _stream()), f"nsff_optflow_{name}")
+    return dst
+
+
+def optflow_down(src):
+    """nsff_optflow_down: one pyramid step, (n, H, W) -> (n, (H+1)//2, (W+1)//2)."""
+    return _optflow_planes("down", src)
+
+
+def optflow_up(src, out_hw):
+    """nsff_optflow_up: (n, h, w) coarse planes to the finer level out_hw = (H, W), values doubled."""
+    return _optflow_planes("up", src, tuple(int(v) for v in out_hw))
+
+
+def optflow_median(src):
+    """nsff_optflow_median: the 3 x 3 median of every (n, H, W) plane, replicated border."""
+    return _optflow_planes("median", src)
+
+
+def optflow_warp(I0, I1, u):
+    """nsff_optflow_warp: I0, I1 (P, H, W), u (2, P, H, W) -> consts (5, P, H, W): Ix | Iy | g | rho_c | I1w."""
+    P, H, W = _planes(I0, "optflow_warp: I0")
+    _dptr(I1, torch.float32, "optflow_warp: I1"), _dptr(u, torch.float32, "optflow_warp: u")
+    if tuple(I1.shape) != (P, H, W) or tuple(u.shape) != (2, P, H, W):
+        raise RuntimeError(f"optflow_warp: I1 {tuple(I1.shape)} / u {tuple(u.shape)} do not go with I0 {(P, H, W)}")
+    consts = torch.empty(5, P, H, W, dtype=torch.float32, device=I0.device)
+    with torch.cuda.device(I0.device):
+        _check(load().nsff_optflow_warp(I0.data_ptr(), I1.data_ptr(), u.data_ptr(), consts.data_ptr(), P, H, W, _stream()),
+               "nsff_optflow_warp")
+    return consts
+
+
+def optflow_result_slot(iters, k):
+    return int(load().nsff_optflow_result_slot(int(iters), int(k)))
+
+
+def optflow_iterate(consts, state, iters, lam=0.15, theta=0.3, tau=0.25, fused=True, tile=0, k=0, other=None):
+    """nsff_optflow_iterate: `iters` TV-L1 iterations from state (6, P, H, W) = u1 | u2 | p11 | p12 | p21 | p22 with consts
+    (5 or 4, P, H, W); returns the new state (one of `state` -- which is overwritten when more than one launch runs -- and `other`,
+    a second buffer of its shape, fresh when None).  fused: k iterations per launch on tile x tile pixels ((0, 0): the default)."""
+    _dptr(consts, torch.float32, "optflow_iterate: consts"), _dptr(state, torch.float32, "optflow_iterate: state")
+    if state.dim() != 4 or state.shape[0] != 6 or consts.dim() != 4 or consts.shape[0] < 4 or consts.shape[1:] != state.shape[1:]:
+        raise RuntimeError(f"optflow_iterate: need state (6, P, H, W) and consts (5, P, H, W), got {tuple(state.shape)} and {tuple(consts.shape)}")
+    other = torch.empty_like(state) if other is None else other
+    _dptr(other, torch.float32, "optflow_iterate: other")
+    if other.shape != state.shape or other.device != state.device or other.data_ptr() == state.data_ptr():
+        raise RuntimeError("optflow_iterate: other must be a second buffer of the state's shape and device")
+    P, H, W = (int(v) for v in state.shape[1:])
+    a = OptflowIterArgs(n_pairs=P, H=H, W=W, iters=int(iters), fused=int(bool(fused)), tile=int(tile), k=int(k), lam=float(lam),
+                        theta=float(theta), tau=float(tau), consts=consts.data_ptr())
+    a.state[0], a.state[1] = state.data_ptr(), other.data_ptr()
+    with torch.cuda.device(state.device):
+        _check(load().nsff_optflow_iterate(C.byref(a), _stream()), "nsff_optflow_iterate")
+    per_launch = (int(k) or OPTFLOW_K) if fused else 1
+    return (state, other)[optflow_result_slot(iters, per_launch)]
+
+
+def optflow_levels(H, W, levels):
+    return int(load().nsff_optflow_levels(int(H), int(W), int(levels)))
+
+
+def optflow_scratch_bytes(n_pairs, H, W, levels):
+    return int(load().nsff_optflow_scratch_bytes(int(n_pairs), int(H), int(W), int(levels)))
+
+
+def optflow(images0, images1, flow, levels=5, warps=5, iters=30, lam=0.15, theta=0.3, tau=0.25, median=True, fused=True, tile=0, k=0,
+            scratch=None):
+    """nsff_optflow: flow (P, H, W, 2) fp32 from images0[p] to images1[p] -- (P, H, W, 3) uint8 or (P, H, W) fp32, both alike.
+    scratch: a uint8 tensor of optflow_scratch_bytes() bytes, any content (a fresh one when None)."""
+    channels = 3 if images0.dtype == torch.uint8 else 1
+    dtype = torch.uint8 if channels == 3 else torch.float32
+    p0, p1 = _dptr(images0, dtype, "optflow: images0"), _dptr(images1, dtype, "optflow: images1")
+    P, H, W = (int(v) for v in images0.shape[:3])
+    dev = images0.device
+    if images1.shape != images0.shape or images1.device != dev or tuple(flow.shape) != (P, H, W, 2) or flow.device != dev:
+        raise RuntimeError(f"optflow: images1 {tuple(images1.shape)} / flow {tuple(flow.shape)} do not go with images0 {tuple(images0.shape)} on {dev}")
+    if scratch is None:
+        scratch = torch.empty(max(optflow_scratch_bytes(P, H, W, levels), 16), dtype=torch.uint8, device=dev)
+    a = OptflowArgs(n_pairs=P, H=H, W=W, channels=channels, levels=int(levels), warps=int(warps), iters=int(iters), median=int(bool(median)),
+                    fused=int(bool(fused)), tile=int(tile), k=int(k), lam=float(lam), theta=float(theta), tau=float(tau),
+                    images0=p0, images1=p1, flow=_dptr(flow, torch.float32, "optflow: flow"),
+                    scratch=_dptr(scratch, torch.uint8, "optflow: scratch"), scratch_bytes=scratch.numel())
+    with torch.cuda.device(dev):
+        _check(load().nsff_optflow(C.byref(a), _stream()), "nsff_optflow")
+    return flow
 
 
 def cdf(weights, out):

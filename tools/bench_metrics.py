@@ -43,6 +43,13 @@ upload, the allocations and both launches).  Byte bounds: the map pass must read
 frame's forward flow is A of its own forward direction and B of the next frame's backward one) and write err and valid of both
 directions and raw (2 x (4 + 1) + 1 B): 27 B per pixel; as issued, without any reuse, it asks for 2 x (8 + 8) B of flow: 43 B
 (`issued_bound`).  The erosion reads and writes one byte per pixel: 2 B (its halo re-reads come from cache).
+TV-L1 optical flow (--only optflow; csrc/optflow.hip) at 512 x 288 on P = 1 and P = 58 pairs (a 30-frame sequence, both
+directions), default parameters (5 levels, 5 warps, 30 iterations, median on): each kernel alone at the finest level (device events
+around one call on preallocated planes), the 30 iterations of one warp there on the plain route and on every built (tile, k) of the
+fused route, taken in turn, and the whole optical_flow call on each route.  Bounds: a launch of the iteration must read the six state
+planes and four of the constants and write the six state planes, 64 B per pixel, whether it runs one iteration (plain: 30 launches a
+warp) or k (fused: ceil(30 / k)): `iter30_*_bound_us` is that traffic at the HBM peak; `redundancy` is the fused route's share of
+repeated arithmetic ((T + 2 k) / T)^2.  No target time: nothing comparable was measured before.
 """
 import argparse
 import json
@@ -411,10 +418,53 @@ def bench_motion(dev, g, W, H, reps, F):
             f"motion_masks_F{F}_call_us": time_us(lambda: motion.motion_masks(fw, bw, K, poses), reps)}
 
 
+OPTFLOW_ITER_BYTES_PER_PIXEL = (6 + 4 + 6) * 4     # one launch of the iteration: state and constants in, state out
+
+
+def bench_optflow(dev, g, W, H, reps, P, iters=30):
+    from nsff_pl_amd import optflow
+    px = P * H * W
+    rgb0 = torch.randint(0, 256, (P, H, W, 3), device=dev, generator=g, dtype=torch.uint8)
+    # a smooth textured pair with a known shift, so that the iteration runs on realistic constants
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    wave = lambda dx, dy: sum(a * torch.sin(ph + fx * (xs - dx) + fy * (ys - dy)) for a, ph, fx, fy in
+                              ((1.0, 0.3, 0.31, 0.12), (0.8, 1.1, -0.22, 0.41), (0.6, 2.0, 0.55, -0.35), (0.9, 0.7, 0.07, 0.63)))
+    I0 = (127.5 + 38 * wave(0.0, 0.0)).expand(P, H, W).contiguous()
+    I1 = (127.5 + 38 * wave(2.0, -0.7)).expand(P, H, W).contiguous()
+    u = torch.zeros(2, P, H, W, device=dev)
+    consts = _lib.optflow_warp(I0, I1, u)
+    state, other = torch.zeros(6, P, H, W, device=dev), torch.empty(6, P, H, W, device=dev)
+    state = _lib.optflow_iterate(consts, state, 5, fused=False, other=other)      # a non-trivial state
+    other = torch.empty_like(state)
+    half = _lib.optflow_down(I0)
+    tag = f"optflow_P{P}"
+    out = {f"{tag}_grey_us": time_us(lambda: _lib.optflow_grey(rgb0), reps),
+           f"{tag}_down_us": time_us(lambda: _lib.optflow_down(I0), reps),
+           f"{tag}_up_us": time_us(lambda: _lib.optflow_up(half, (H, W)), reps),
+           f"{tag}_warp_us": time_us(lambda: _lib.optflow_warp(I0, I1, u), reps),
+           f"{tag}_median_us": time_us(lambda: _lib.optflow_median(I0), reps)}
+    routes = [("plain", dict(fused=False))] + [(f"fused_T{t}_K{k}", dict(fused=True, tile=t, k=k)) for t, k in _lib.OPTFLOW_PAIRS]
+    times = time_alternating_us([lambda kw=kw: _lib.optflow_iterate(consts, state, iters, other=other, **kw) for _, kw in routes], reps)
+    for (name, kw), t in zip(routes, times):
+        launches = -(-iters // kw.get("k", 1))
+        out[f"{tag}_iter{iters}_{name}_us"] = t
+        out[f"{tag}_iter{iters}_{name}_bound_us"] = px * OPTFLOW_ITER_BYTES_PER_PIXEL * launches / HBM_PEAK * 1e6
+        if kw["fused"]:
+            out[f"{tag}_{name}_redundancy"] = ((kw["tile"] + 2 * kw["k"]) / kw["tile"]) ** 2
+    scratch = torch.empty(optflow.scratch_bytes(P, H, W), dtype=torch.uint8, device=dev)
+    flow = torch.empty(P, H, W, 2, device=dev)
+    rgb1 = torch.roll(rgb0, (1, 2), (1, 2))
+    calls = time_alternating_us([lambda kw=kw: _lib.optflow(rgb0, rgb1, flow, scratch=scratch, **kw) for _, kw in routes], max(reps // 5, 3), warmup=2)
+    for (name, _), t in zip(routes, calls):
+        out[f"{tag}_call_{name}_us"] = t
+    out[f"{tag}_call_default_us"] = time_us(lambda: optflow.optical_flow(rgb0, rgb1), max(reps // 5, 3), warmup=2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion (default: everything but lpips)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion, optflow (default: everything but lpips and optflow)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -449,6 +499,10 @@ def main():
         if "motion" in only:
             for F in (1, 30):
                 out.update(bench_motion(dev, g, W, H, args.reps, F))
+        if "optflow" in only:
+            for P in (1, 58):
+                out.update(bench_optflow(dev, g, W, H, args.reps, P))
+                torch.cuda.empty_cache()
         print(json.dumps({k: (round(v, 2) if v >= 0.01 else float(f"{v:.3g}")) if isinstance(v, float) else v for k, v in out.items()}))
         return
     gt = torch.rand(H, W, 3, device=dev, generator=g)
