@@ -1106,6 +1106,96 @@ int     nsff_optflow_levels(int32_t H, int32_t W, int32_t levels);
 int64_t nsff_optflow_scratch_bytes(int32_t n_pairs, int32_t H, int32_t W, int32_t levels);
 int     nsff_optflow(const NsffOptflowArgs* args, void* stream);
 
+/* ---- disparity from optical flow and camera poses (csrc/depth.hip; nsff_pl_amd/depth.py): the classical
+ * stand-in for the reference's DPT step (preprocess.py:106-115).  For a static pixel flow plus two poses is a depth measurement
+ * (motion parallax); where there is none an image-guided fill gives a dense map.  Entry points added without a change of
+ * NSFF_ABI_VERSION: nothing that existed changes.  Every array is fp32 unless said otherwise, every plane (F, H, W) contiguous, and
+ * every step below ONE fp32 operation in the order written (the file is built -ffp-contract=off; IEEE division), which the tests
+ * compare bit for bit with numpy.  No atomics on floats, no device-side convergence test, no data-dependent loop, no
+ * synchronisation, no allocation: every call is a fixed list of launches and capturable; the frame is a grid dimension of every
+ * kernel.  Common refusals, all before a launch: a size outside the stated range, a bad flag or value or a scratch that is too
+ * small NSFF_ERR_INVALID; a missing pointer NSFF_ERR_NULL; an array off its alignment NSFF_ERR_ALIGN.
+ *
+ * sparse   one launch for n_frames frames and both directions (0 forward: neighbour f + 1, flow_fw[f]; 1 backward: f - 1,
+ *          flow_bw[f]); flows (F, H*W, 2) pixels.  Pm (F, 2, 12): per frame and direction the nine entries of G = M_n M_f^-1,
+ *          row-major, and the three of e = M_n (C_f - C_n), with M = K diag(1,-1,-1) R^-1 and C the camera centre: a pixel (x, y, 1)
+ *          of f at depth 1 / delta appears in n at delta * e + h, h = G (x, y, 1).  A row of twelve zeros: no vote (no neighbour,
+ *          coincident centres).  At the pixel (x, y), integers as floats, per direction with the flow (u, v):
+ *            hx = (G[0] * x + G[1] * y) + G[2];  hy = (G[3] * x + G[4] * y) + G[5];  hz = (G[6] * x + G[7] * y) + G[8]
+ *            up = x + u;  vp = y + v;  r = 1f / hz
+ *            ax = (e[0] - up * e[2]) * r;  ay = (e[1] - vp * e[2]) * r
+ *            bx = up - hx * r;  by = vp - hy * r             (the parallax in pixels against the point at infinity)
+ *            p2 = bx * bx + by * by;  ab = ax * bx + ay * by;  aa = ax * ax + ay * ay
+ *            vote = row non-zero && |u|, |v| <= 1e7 (a NaN is not) && (valid == NULL || valid[f][d] != 0)
+ *                   && (masks == NULL || masks[f] != 0) && hz > 0 && p2 >= min_parallax * min_parallax (fp32, formed on the host)
+ *          and over the directions in the order fw, bw, each sum from 0:  num += vote ? ab : 0;  den += vote ? aa : 0;
+ *          par += vote ? p2 : 0.  known = den > 0 && num > 0;  c = known ? par : 0 (the confidence, px^2);
+ *          n = known ? par * (num / den) : 0 (so that the disparity is n / c).  valid (F, 2, H*W) uint8 and masks (F, H*W) uint8
+ *          (0 dynamic, the polarity of nsff_motion_maps) are optional.  counts (F) int64, optional: the known pixels of each
+ *          frame, an exact integer through the per-frame reduction; it needs `scratch`, nsff_disparity_sparse_scratch_bytes bytes,
+ *          16-byte aligned, ZERO before its first use and left zero.  n_frames <= 65535, 1 <= H * W < 2^31; min_parallax >= 0;
+ *          flows and counts 8-byte aligned.
+ * push     one pyramid step of the planes c, n and grey, (F, H, W) -> (F, (H+1)/2, (W+1)/2): each coarse pixel takes the 2 x 2
+ *          block of the finer level, clipped at the image, in row-major order -- s = v00; s = s + v01; s = s + v10; s = s + v11,
+ *          the terms that exist -- c' = the sum of c, n' of n, grey' = the sum of grey / the block's pixel count.  Not for 1 x 1.
+ * pull     one step down: d = c > 0 ? n / c : parent[y >> 1][x >> 1], parent the (F, (H+1)/2, (W+1)/2) level above; parent NULL
+ *          (the 1 x 1 top): 0 in its place; c and n NULL: d = the parent's value alone, the nearest-neighbour upsampling.
+ * relax    `iters` weighted-Jacobi iterations of d on the planes n, c and the guide grey:
+ *            g_q = 1f / (1f + t * t), t = (grey_p - grey_q) / sigma, for the neighbours q = left, right, up, down inside the image,
+ *            0 for those outside;  S = 0, Wt = 0, then in that order  S = S + (inside ? g_q * d_q : 0);  Wt = Wt + g_q
+ *            num = n + lambda * S;  den = c + lambda * Wt;  d' = den > 0 ? num / den : d
+ *          The iterations go back and forth between state[0] (the input) and state[1]; the result is in
+ *          state[nsff_disparity_result_slot(iters, fused ? k : 1)].  fused == 0: one launch per iteration, the definition.
+ *          fused == 1: k iterations per launch on a tile x tile block of pixels held in LDS with a halo of k pixels, bit-identical
+ *          to the plain route for every iters (a last launch runs iters % k); (tile, k) one of the built pairs, (16, 2), (32, 2),
+ *          (32, 3), (32, 4), (32, 6), or (0, 0) = NSFF_DISPARITY_TILE, NSFF_DISPARITY_K.  The weights are recomputed from grey
+ *          (an iteration reads d, n, c, grey and writes d: 20 bytes a pixel).  0 <= iters <= 100000; lambda >= 0, sigma > 0, finite;
+ *          n_frames * H * W < 2^31.
+ * nsff_disparity_dense: the whole densification of F frames from n, c and grey: push to the 1 x 1 top, level after level
+ *          (nsff_disparity_levels of them, the finest being level 0); pull from the top down to level `levels` (the top itself
+ *          where levels equals their number); then at each of the finest `levels` levels, coarse to fine, the nearest-neighbour
+ *          upsampling of the level above (at the top: its own pulled value) as the start of `iters` relax iterations.  disps
+ *          (F, H, W): the result.  A frame without a known pixel comes out all zero.  1 <= levels <= nsff_disparity_levels(H, W);
+ *          scratch: nsff_disparity_dense_scratch_bytes bytes (0 = the shape is refused), 16-byte aligned, any content. */
+#define NSFF_DISPARITY_TILE   32   /* the fused route's default tile side ...                                    */
+#define NSFF_DISPARITY_K      3    /* ... and iterations per launch (DESIGN.md section 11.5 has the measurement) */
+#define NSFF_DISPARITY_FUSED  1    /* the route nsff_pl_amd.depth takes when not told: 1 fused, 0 plain          */
+typedef struct NsffDisparitySparseArgs {
+    int32_t n_frames, H, W;
+    float   min_parallax;
+    const float* flow_fw;  const float* flow_bw;  const float* Pm;
+    const uint8_t* valid;  const uint8_t* masks;
+    float* n;  float* c;  int64_t* counts;
+    void* scratch;  int64_t scratch_bytes;
+} NsffDisparitySparseArgs;
+typedef struct NsffDisparityRelaxArgs {
+    int32_t n_frames, H, W, iters;
+    int32_t fused, tile, k, pad_;
+    float   lambda, sigma;
+    const float* n;  const float* c;  const float* grey;  float* state[2];
+} NsffDisparityRelaxArgs;
+typedef struct NsffDisparityDenseArgs {
+    int32_t n_frames, H, W, levels;
+    int32_t iters, fused, tile, k;
+    float   lambda, sigma;
+    const float* n;  const float* c;  const float* grey;  float* disps;
+    void* scratch;  int64_t scratch_bytes;
+} NsffDisparityDenseArgs;
+int64_t nsff_disparity_sparse_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int     nsff_disparity_sparse(const NsffDisparitySparseArgs* args, void* stream);
+int     nsff_disparity_push(const float* c, const float* n, const float* grey, float* c2, float* n2, float* grey2, int32_t n_frames,
+                            int32_t H, int32_t W, void* stream);
+int     nsff_disparity_pull(const float* c, const float* n, const float* parent, float* d, int32_t n_frames, int32_t H, int32_t W,
+                            void* stream);
+int     nsff_disparity_relax(const NsffDisparityRelaxArgs* args, void* stream);
+/* host only: 0 or 1, the state buffer that holds the result of `iters` iterations run k per launch (k = 1: the plain route);
+ * negative for iters < 0 or k < 1 */
+int     nsff_disparity_result_slot(int32_t iters, int32_t k);
+/* host only: the number of levels of the pyramid of an H x W image down to 1 x 1 (0: a refused shape) */
+int     nsff_disparity_levels(int32_t H, int32_t W);
+int64_t nsff_disparity_dense_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int     nsff_disparity_dense(const NsffDisparityDenseArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

@@ -23,6 +23,8 @@ from . import motion
 from .motion import motion_masks, flow_consistency, fundamental_matrices
 from . import optflow
 from .optflow import optical_flow, sequence_flows
+from . import depth
+from .depth import disparity_maps, triangulate, densify, parallax_matrices, sequence_geometry
 from . import panels
 from .panels import validation_panels, error_blend
 from .lpips import LPIPS
@@ -37,5 +39,6 @@ __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "
            "tracks", "advect", "draw",
            "motion", "motion_masks", "flow_consistency", "fundamental_matrices",
            "optflow", "optical_flow", "sequence_flows",
+           "depth", "disparity_maps", "triangulate", "densify", "parallax_matrices", "sequence_geometry",
            "panels", "validation_panels", "error_blend", "LPIPS",
            "scene", "nearest_depth", "scene_from_colmap", "visibility_matrix"]

@@ -259,8 +259,31 @@ class OptflowArgs(C.Structure):
                 ("images0", _fp), ("images1", _fp), ("flow", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+DISPARITY_TILE, DISPARITY_K, DISPARITY_FUSED = 32, 3, 1                        # NSFF_DISPARITY_*
+DISPARITY_PAIRS = ((16, 2), (32, 2), (32, 3), (32, 4), (32, 6))               # the (tile, k) the fused relaxation is built for
+
+
+class DisparitySparseArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("min_parallax", C.c_float),
+                ("flow_fw", _fp), ("flow_bw", _fp), ("Pm", _fp), ("valid", _fp), ("masks", _fp), ("n", _fp), ("c", _fp), ("counts", _fp),
+                ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
+class DisparityRelaxArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("iters", C.c_int32),
+                ("fused", C.c_int32), ("tile", C.c_int32), ("k", C.c_int32), ("pad_", C.c_int32),
+                ("lam", C.c_float), ("sigma", C.c_float), ("n", _fp), ("c", _fp), ("grey", _fp), ("state", _fp * 2)]
+
+
+class DisparityDenseArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("levels", C.c_int32),
+                ("iters", C.c_int32), ("fused", C.c_int32), ("tile", C.c_int32), ("k", C.c_int32),
+                ("lam", C.c_float), ("sigma", C.c_float), ("n", _fp), ("c", _fp), ("grey", _fp), ("disps", _fp),
+                ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
 RAY_RECORD = 16
-_DRAW_OUT = ["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
+_DRAW_OUT =["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
 
 class RayDrawArgs(C.Structure):
@@ -408,6 +431,15 @@ _SIGNATURES = {
     "nsff_optflow_levels": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_optflow_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "nsff_optflow": (C.c_int, [C.POINTER(OptflowArgs), _fp]),
+    "nsff_disparity_sparse_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_disparity_sparse": (C.c_int, [C.POINTER(DisparitySparseArgs), _fp]),
+    "nsff_disparity_push": (C.c_int, [_fp] * 6 + [C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "nsff_disparity_pull": (C.c_int, [_fp] * 4 + [C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "nsff_disparity_relax": (C.c_int, [C.POINTER(DisparityRelaxArgs), _fp]),
+    "nsff_disparity_result_slot": (C.c_int, [C.c_int32, C.c_int32]),
+    "nsff_disparity_levels": (C.c_int, [C.c_int32, C.c_int32]),
+    "nsff_disparity_dense_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_disparity_dense": (C.c_int, [C.POINTER(DisparityDenseArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1604,6 +1636,119 @@ def optflow(images0, images1, flow, levels=5, warps=5, iters=30, lam=0.15, theta
     with torch.cuda.device(dev):
         _check(load().nsff_optflow(C.byref(a), _stream()), "nsff_optflow")
     return flow
+
+
+# ---- disparity from flow and poses (csrc/depth.hip).  Planes are contiguous fp32 (F, H, W) GPU tensors.
+def disparity_sparse_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_disparity_sparse_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def disparity_sparse(flows_fw, flows_bw, Pm, valid=None, masks=None, min_parallax=0.5, counts=None, scratch=None):
+    """nsff_disparity_sparse on (F, H, W, 2) fp32 flows with the parallax rows Pm (F, 2, 12) fp32, valid (F, 2, H, W) uint8 and masks
+    (F, H, W) uint8 optional -> (n, c), each (F, H, W) fp32; counts (F,) int64: the known pixels of each frame.  scratch: a uint8
+    tensor of disparity_sparse_scratch_bytes() bytes, zero before its first use (a fresh one when None)."""
+    require_gpu_tensor(flows_fw, "disparity_sparse: flows_fw")
+    F, H, W = (int(v) for v in flows_fw.shape[:3])
+    px, dev = F * H * W, flows_fw.device
+    n, c = (torch.empty(F, H, W, dtype=torch.float32, device=dev) for _ in range(2))
+    a = DisparitySparseArgs(n_frames=F, H=H, W=W, min_parallax=float(min_parallax), n=n.data_ptr(), c=c.data_ptr())
+    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, px * 2), ("flow_bw", flows_bw, torch.float32, px * 2),
+                                   ("Pm", Pm, torch.float32, F * 24), ("valid", valid, torch.uint8, px * 2),
+                                   ("masks", masks, torch.uint8, px), ("counts", counts, torch.int64, F)):
+        if t is None:
+            continue
+        ptr = _dptr(t, dtype, f"disparity_sparse: {field}")
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"disparity_sparse: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        setattr(a, field, ptr)
+    if counts is not None and scratch is None:
+        scratch = torch.zeros(max(disparity_sparse_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    if scratch is not None:
+        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "disparity_sparse: scratch"), scratch.numel()
+    with torch.cuda.device(dev):
+        _check(load().nsff_disparity_sparse(C.byref(a), _stream()), "nsff_disparity_sparse")
+    return n, c
+
+
+def _same_planes(who, first, **others):
+    shape = _planes(first, f"{who}: c")
+    for name, t in others.items():
+        if _planes(t, f"{who}: {name}") != shape or t.device != first.device:
+            raise RuntimeError(f"{who}: {name} {tuple(t.shape)} on {t.device} does not go with c {shape} on {first.device}")
+    return shape
+
+
+def disparity_push(c, n, grey):
+    """nsff_disparity_push: one pyramid step of the planes c, n, grey, (F, H, W) -> (F, (H+1)//2, (W+1)//2) each."""
+    F, H, W = _same_planes("disparity_push", c, n=n, grey=grey)
+    out = tuple(torch.empty(F, (H + 1) // 2, (W + 1) // 2, dtype=torch.float32, device=c.device) for _ in range(3))
+    with torch.cuda.device(c.device):
+        _check(load().nsff_disparity_push(c.data_ptr(), n.data_ptr(), grey.data_ptr(), *(t.data_ptr() for t in out), F, H, W, _stream()),
+               "nsff_disparity_push")
+    return out
+
+
+def disparity_pull(c, n, parent, hw=None):
+    """nsff_disparity_pull: d = n / c where c > 0, else the parent's value at (y >> 1, x >> 1) (parent None: 0).  c and n None: the
+    nearest-neighbour upsampling of parent to hw = (H, W)."""
+    if c is None:
+        F, (H, W) = _planes(parent, "disparity_pull: parent")[0], (int(v) for v in hw)
+        dev = parent.device
+    else:
+        F, H, W = _same_planes("disparity_pull", c, n=n)
+        dev = c.device
+    if parent is not None and (_planes(parent, "disparity_pull: parent") != (F, (H + 1) // 2, (W + 1) // 2) or parent.device != dev):
+        raise RuntimeError(f"disparity_pull: parent {tuple(parent.shape)} is not the level above {(F, H, W)}")
+    d = torch.empty(F, H, W, dtype=torch.float32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        _check(load().nsff_disparity_pull(ptr(c), ptr(n), ptr(parent), d.data_ptr(), F, H, W, _stream()), "nsff_disparity_pull")
+    return d
+
+
+def disparity_result_slot(iters, k):
+    return int(load().nsff_disparity_result_slot(int(iters), int(k)))
+
+
+def disparity_relax(d, n, c, grey, iters, lam=8.0, sigma=12.75, fused=False, tile=0, k=0, other=None):
+    """nsff_disparity_relax: `iters` weighted-Jacobi iterations from d (F, H, W) with the planes n, c and the guide grey; returns the
+    new d (one of `d` -- which is overwritten when more than one launch runs -- and `other`, a second buffer of its shape, fresh
+    when None).  fused: k iterations per launch on tile x tile pixels ((0, 0): the default pair)."""
+    F, H, W = _same_planes("disparity_relax", c, n=n, grey=grey, d=d)
+    other = torch.empty_like(d) if other is None else other
+    _dptr(other, torch.float32, "disparity_relax: other")
+    if other.shape != d.shape or other.device != d.device or other.data_ptr() == d.data_ptr():
+        raise RuntimeError("disparity_relax: other must be a second buffer of d's shape and device")
+    a = DisparityRelaxArgs(n_frames=F, H=H, W=W, iters=int(iters), fused=int(bool(fused)), tile=int(tile), k=int(k), lam=float(lam),
+                           sigma=float(sigma), n=n.data_ptr(), c=c.data_ptr(), grey=grey.data_ptr())
+    a.state[0], a.state[1] = d.data_ptr(), other.data_ptr()
+    with torch.cuda.device(d.device):
+        _check(load().nsff_disparity_relax(C.byref(a), _stream()), "nsff_disparity_relax")
+    per_launch = (int(k) or DISPARITY_K) if fused else 1
+    return (d, other)[disparity_result_slot(iters, per_launch)]
+
+
+def disparity_levels(H, W):
+    return int(load().nsff_disparity_levels(int(H), int(W)))
+
+
+def disparity_dense_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_disparity_dense_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def disparity_dense(n, c, grey, disps, levels=3, iters=30, lam=8.0, sigma=12.75, fused=False, tile=0, k=0, scratch=None):
+    """nsff_disparity_dense: disps (F, H, W) fp32 from the planes n, c and the guide grey.  scratch: a uint8 tensor of
+    disparity_dense_scratch_bytes() bytes, any content (a fresh one when None)."""
+    F, H, W = _same_planes("disparity_dense", c, n=n, grey=grey, disps=disps)
+    dev = c.device
+    if scratch is None:
+        scratch = torch.empty(max(disparity_dense_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    a = DisparityDenseArgs(n_frames=F, H=H, W=W, levels=int(levels), iters=int(iters), fused=int(bool(fused)), tile=int(tile), k=int(k),
+                           lam=float(lam), sigma=float(sigma), n=n.data_ptr(), c=c.data_ptr(), grey=grey.data_ptr(), disps=disps.data_ptr(),
+                           scratch=_dptr(scratch, torch.uint8, "disparity_dense: scratch"), scratch_bytes=scratch.numel())
+    with torch.cuda.device(dev):
+        _check(load().nsff_disparity_dense(C.byref(a), _stream()), "nsff_disparity_dense")
+    return disps
 
 
 def cdf(weights, out):

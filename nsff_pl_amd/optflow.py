@@ -4,8 +4,8 @@ The reference gets its ``flow_fw`` / ``flow_bw`` from RAFT (preprocess.py:106-12
 ship nor run.  This module is a CLASSICAL STAND-IN, not RAFT's flow: TV-L1 (Zach, Pock and Bischof 2007, in the fixed-iteration
 form of Sanchez, Meinhardt-Llopis and Facciolo, IPOL 2013) on a grey pyramid -- stencils and point-wise arithmetic only,
 deterministic, no host synchronisation.  With it the chain images -> :func:`nsff_pl_amd.frames.resize_images` -> flow ->
-:func:`nsff_pl_amd.motion.flow_consistency` -> :func:`nsff_pl_amd.motion.motion_masks` -> ray records needs no network but the
-one for monocular disparity.
+:func:`nsff_pl_amd.motion.flow_consistency` -> :func:`nsff_pl_amd.motion.motion_masks` -> ray records needs no network; the
+monocular disparity has a classical stand-in of its own, :mod:`nsff_pl_amd.depth`.
 
 * :func:`optical_flow`   -- (P, H, W, 2) fp32: the pixel motion from ``images0[p]`` to ``images1[p]``, x first;
 * :func:`sequence_flows` -- ``{'flows_fw', 'flows_bw'[, 'valid']}`` of F frames in the reference's convention, both directions as

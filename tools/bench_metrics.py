@@ -50,6 +50,14 @@ fused route, taken in turn, and the whole optical_flow call on each route.  Boun
 planes and four of the constants and write the six state planes, 64 B per pixel, whether it runs one iteration (plain: 30 launches a
 warp) or k (fused: ceil(30 / k)): `iter30_*_bound_us` is that traffic at the HBM peak; `redundancy` is the fused route's share of
 repeated arithmetic ((T + 2 k) / T)^2.  No target time: nothing comparable was measured before.
+Disparity from flow and poses (--only disparity; csrc/depth.hip) at 512 x 288 on F = 1 and F = 30 frames, default parameters (3 levels,
+30 iterations, lambda 8, sigma 12.75): nsff_disparity_sparse alone with valid, masks and its counts (it must read both flows, two
+validity bytes and a mask byte and write n and c: 8 + 8 + 2 + 1 + 4 + 4 = 27 B per pixel), the 30 relax iterations of the finest level
+on the plain route and on every built (tile, k) of the fused route, taken in turn (a launch reads d, n, c and the grey guide and
+writes d, 20 B per pixel, whether it runs one iteration or k: `relax30_*_bound_us` is that traffic at the HBM peak; `redundancy` is
+((T + 2 k) / T)^2), the whole nsff_disparity_dense call on each route, and depth.disparity_maps with its default route (host-side
+parallax rows, their upload, the grey stage and the allocations included).  --only disparity_resources needs no GPU: the
+compiler's report of VGPRs, scratch, LDS and waves per SIMD of every kernel of csrc/depth.hip.
 """
 import argparse
 import json
@@ -461,11 +469,85 @@ def bench_optflow(dev, g, W, H, reps, P, iters=30):
     return out
 
 
+DISPARITY_SPARSE_BYTES_PER_PIXEL = 8 + 8 + 2 + 1 + 4 + 4     # both flows, valid of both directions, the mask in; n and c out
+DISPARITY_RELAX_BYTES_PER_PIXEL = (4 + 1) * 4                # one launch of the relaxation: d, n, c, grey in, d out
+
+
+def bench_disparity(dev, g, W, H, reps, F, iters=30):
+    from nsff_pl_amd import depth
+    px = F * H * W
+    K = np.array([[400.0, 0, W / 2], [0, 400.0, H / 2], [0, 0, 1]])
+    poses = np.tile(np.eye(4)[:3], (F + 1, 1, 1))                # one pose more than frames, so that F = 1 has a neighbour's row
+    poses[:, 0, 3] = 0.1 * np.arange(F + 1)
+    Pm = depth.parallax_matrices(K, poses)[:F].contiguous().to(dev)
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    delta = 0.3 + 0.1 * torch.sin(0.02 * xs + 0.03 * ys)         # a smooth disparity map: the flow is its parallax, 40 delta px, and noise
+    fw = torch.stack([-40.0 * delta, torch.zeros_like(delta)], -1).expand(F, H, W, 2) + 0.05 * torch.randn(F, H, W, 2, device=dev, generator=g)
+    bw = -fw + 0.05 * torch.randn(F, H, W, 2, device=dev, generator=g)
+    valid = (torch.rand(F, 2, H, W, device=dev, generator=g) < 0.9).to(torch.uint8)
+    masks = torch.where((xs - W / 2) ** 2 + (ys - H / 2) ** 2 < (0.2 * H) ** 2, 0, 255).to(torch.uint8).expand(F, H, W).contiguous()
+    grey = (127.5 + 38 * (torch.sin(0.31 * xs + 0.12 * ys) + 0.8 * torch.sin(1.1 - 0.22 * xs + 0.41 * ys))).expand(F, H, W).contiguous()
+    rgb = grey.clamp(0, 255).to(torch.uint8)[..., None].expand(F, H, W, 3).contiguous()
+    counts = torch.empty(F, dtype=torch.int64, device=dev)
+    small = torch.zeros(_lib.disparity_sparse_scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    sparse = lambda: _lib.disparity_sparse(fw, bw, Pm, valid=valid, masks=masks, counts=counts, scratch=small)
+    n, c = sparse()
+    tag = f"disparity_F{F}"
+    out = {f"{tag}_known_fraction": float(counts.sum()) / px,
+           f"{tag}_sparse_us": time_us(sparse, reps),
+           f"{tag}_sparse_bound_us": px * DISPARITY_SPARSE_BYTES_PER_PIXEL / HBM_PEAK * 1e6}
+    d, other = torch.full((F, H, W), 0.3, device=dev), torch.empty(F, H, W, device=dev)
+    routes = [("plain", dict(fused=False))] + [(f"fused_T{t}_K{k}", dict(fused=True, tile=t, k=k)) for t, k in _lib.DISPARITY_PAIRS]
+    times = time_alternating_us([lambda kw=kw: _lib.disparity_relax(d, n, c, grey, iters, other=other, **kw) for _, kw in routes], reps)
+    for (name, kw), t in zip(routes, times):
+        launches = -(-iters // kw.get("k", 1))
+        out[f"{tag}_relax{iters}_{name}_us"] = t
+        out[f"{tag}_relax{iters}_{name}_bound_us"] = px * DISPARITY_RELAX_BYTES_PER_PIXEL * launches / HBM_PEAK * 1e6
+        if kw["fused"]:
+            out[f"{tag}_{name}_redundancy"] = ((kw["tile"] + 2 * kw["k"]) / kw["tile"]) ** 2
+    scratch = torch.empty(depth.scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    disps = torch.empty(F, H, W, device=dev)
+    calls = time_alternating_us([lambda kw=kw: _lib.disparity_dense(n, c, grey, disps, iters=iters, scratch=scratch, **kw) for _, kw in routes], reps)
+    for (name, _), t in zip(routes, calls):
+        out[f"{tag}_dense_{name}_us"] = t
+    poses_F = poses[:F] if F > 1 else poses[:1]
+    out[f"{tag}_maps_call_default_us"] = time_us(lambda: depth.disparity_maps(rgb, fw, bw, K, poses_F, masks=masks, valid=valid), reps)
+    return out
+
+
+def disparity_resources():
+    """The compiler's resource report of every kernel of csrc/depth.hip: {kernel: [VGPRs, scratch bytes, LDS bytes, waves per SIMD]}."""
+    import re
+    import subprocess
+    import tempfile
+    csrc = os.path.join(ROOT, "nsff_pl_amd", "csrc")
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+               "-Rpass-analysis=kernel-resource-usage", "-c", "depth.hip", "-o", os.path.join(tmp, "depth.o")]
+        text = subprocess.run(cmd, cwd=csrc, check=True, capture_output=True, text=True).stderr
+    out, name = {}, None
+    for line in text.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = re.sub(r"^_ZN\d+_GLOBAL__N_1\d+", "", m.group(1))
+            t = re.match(r"([a-z_]+?)(?:ILi(\d+)ELi(\d+)EE|E)", name)
+            name = f"{t.group(1)}<{t.group(2)}, {t.group(3)}>" if t and t.group(2) else (t.group(1) if t else name)
+            out[name] = [None] * 4
+        for i, key in enumerate(("VGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")):
+            m = re.search(re.escape(key) + r": (\d+)", line)
+            if m and name and "Agpr" not in line:
+                out[name][i] = int(m.group(1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion, optflow (default: everything but lpips and optflow)")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion, optflow, disparity (default: everything but lpips, optflow and disparity); disparity_resources alone needs no GPU")
     args = ap.parse_args()
+    if args.only == "disparity_resources":
+        print(json.dumps(disparity_resources()))
+        return
     dev = torch.device("cuda:0")
     W, H = 512, 288
     px = W * H
@@ -502,6 +584,10 @@ def main():
         if "optflow" in only:
             for P in (1, 58):
                 out.update(bench_optflow(dev, g, W, H, args.reps, P))
+                torch.cuda.empty_cache()
+        if "disparity" in only:
+            for F in (1, 30):
+                out.update(bench_disparity(dev, g, W, H, args.reps, F))
                 torch.cuda.empty_cache()
         print(json.dumps({k: (round(v, 2) if v >= 0.01 else float(f"{v:.3g}")) if isinstance(v, float) else v for k, v in out.items()}))
         return
