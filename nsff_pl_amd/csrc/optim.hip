@@ -68,9 +68,14 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float4* __restrict__ p, 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             if (!((live >> c) & 1u)) continue;
-            const float gr = G[c] + wd * P[c];                         // L2 penalty folded into the gradient (torch Adam)
-            M[c] = M[c] + w1 * (gr - M[c]);                           // exp_avg.lerp_(grad, 1 - beta1)
-            V[c] = V[c] * beta2 + w2 * gr * gr;                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+            // The moments take the roundings of torch.optim.Adam's default device path (its _foreach_ kernels, which the compiler
+            // contracts): one fma where torch has one, and (1 - beta2) (g g), not ((1 - beta2) g) g.  Measured on the MI355X against
+            // torch 2.10 on 2.1 M elements: both moments bit for bit after one step and after two (EXPERIMENTS.md R18); written
+            // separately, exp_avg differed from torch's in 30 % of the elements and, where its two terms cancel, by more than
+            // 2e-6 of its value.  (This file is built with -ffp-contract=off: nothing else fuses.)
+            const float gr = fmaf(wd, P[c], G[c]);                     // _foreach_add(grads, params, alpha=weight_decay)
+            M[c] = fmaf(w1, gr - M[c], M[c]);                          // _foreach_lerp_(exp_avgs, grads, 1 - beta1)
+            V[c] = fmaf(w2, gr * gr, V[c] * beta2);                    // _foreach_mul_(exp_avg_sqs, beta2); _foreach_addcmul_(.., grads, grads, 1 - beta2)
             const float denom = sqrtf(V[c]) / sqrt_bc2 + eps;
             P[c] = P[c] - step_size * (M[c] / denom);
         }

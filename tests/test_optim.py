@@ -169,6 +169,65 @@ def test_native_adam_skips_parameters_without_gradient_like_torch_adam(hip_lib):
             np.testing.assert_array_equal(a, start[k])
 
 
+WRAP_FIRST = 2048 * 256 * 4                 # adam_step_kernel / adam_used_kernel run at most 2048 workgroups of 256 float4s:
+WRAP_N = WRAP_FIRST + 1024 + 3              # from element WRAP_FIRST on their grid-stride loops take a second trip
+WRAP_SIZES = (1000001, WRAP_FIRST + 515 - 1000001, 1024 + 3 - 515)
+
+
+@pytest.mark.gpu
+def test_native_adam_wraps_the_stride_loop(hip_lib):
+    """The Adam counterpart of test_optim_options.py::test_native_steps_wrap_the_stride_loop, at the size of the reference model
+    pair (2.3 M parameters: the wrap is the production case), in the segment form (weight_decay 0.01): three tensors, the second
+    boundary inside the wrapped tail at an element that is not float4-aligned, the last tensor without a gradient.  Two steps
+    against torch.optim.Adam -- values and both moments -- at this file's bound.
+
+    exp_avg after two steps is w (1 - w) g1' + w g2' with terms of about 0.1; where they cancel, one ulp of a term (7e-9) is more
+    than 2e-6 of the value, so exp_avg holds this bound only because adam_step_kernel rounds the moments as torch's kernels do
+    (csrc/optim.hip; EXPERIMENTS.md R18: with its own roundings it was outside on 3 940 of 2 097 667 elements, as torch's fp32
+    run is against its float64 run on 10 690)."""
+    dev = torch.device("cuda:0")
+    assert sum(WRAP_SIZES) == WRAP_N and min(WRAP_SIZES) > 0
+    b1, b2 = WRAP_SIZES[0], WRAP_SIZES[0] + WRAP_SIZES[1]
+    assert WRAP_FIRST < b2 < WRAP_N and b2 % 4 != 0 and b1 % 4 != 0
+    g = torch.Generator().manual_seed(5)
+    start = [torch.randn(n, generator=g) * 0.3 for n in WRAP_SIZES]
+    grads = [[torch.randn(n, generator=g).to(dev) for n in WRAP_SIZES[:2]] for _ in range(2)]
+    pf = [torch.nn.Parameter(s.to(dev)) for s in start]
+    pt = [torch.nn.Parameter(s.to(dev)) for s in start]
+    of, ot = FlatAdam(pf, lr=5e-4, eps=1e-8, weight_decay=0.01), _torch_adam(pt, 0.01)
+    assert of.flat_param.numel() == WRAP_N + 1 and of._segments()[0] is not None
+    for step in grads:
+        for k, gr in enumerate(step):                       # (the third tensor: .grad None in torch, a zero slice here)
+            pf[k].grad.copy_(gr)
+            pt[k].grad = gr.clone()
+        of.step(); ot.step()
+    torch.cuda.synchronize()
+    assert float(of.state[0]) == 2.0
+    off = 0
+    for k, n in enumerate(WRAP_SIZES):
+        got = {"param": pf[k].detach().cpu(), "exp_avg": of.exp_avg[off:off + n].cpu(), "exp_avg_sq": of.exp_avg_sq[off:off + n].cpu()}
+        if k < 2:
+            want = {"param": pt[k].detach().cpu(), "exp_avg": ot.state[pt[k]]["exp_avg"].cpu(), "exp_avg_sq": ot.state[pt[k]]["exp_avg_sq"].cpu()}
+            for name in got:
+                a, b = got[name].numpy(), want[name].numpy()
+                diff = np.abs(a.astype(np.float64) - b)
+                print(f"tensor {k} {name}: outside rtol 2e-6 / atol 1e-9 on {int((diff > 2e-6 * np.abs(b) + 1e-9).sum())} of {a.size} elements, "
+                      f"largest |difference| {diff.max():.3g}, bits differ on {int((a != b).sum())}")
+                np.testing.assert_allclose(a, b, rtol=2e-6, atol=1e-9, err_msg=f"tensor {k} {name}")
+        else:                                               # unused: torch keeps no state for it; value and moments keep their bits
+            assert pt[k] not in ot.state or not ot.state[pt[k]]
+            assert torch.equal(got["param"].view(torch.int32), start[k].view(torch.int32))
+            assert torch.equal(pt[k].detach().cpu().view(torch.int32), start[k].view(torch.int32))
+            assert not got["exp_avg"].any() and not got["exp_avg_sq"].any()
+        off += n
+    # the middle tensor's part of the wrapped tail was stepped, every element of it (a pass over the first trip alone, or one
+    # that stops at the last aligned float4 before the boundary, leaves elements where they were)
+    tail = pf[1].detach().cpu()[WRAP_FIRST - b1:]
+    assert tail.numel() == 515 and bool((tail != start[1][WRAP_FIRST - b1:]).all())
+    for buf in (of.flat_param, of.exp_avg, of.exp_avg_sq):  # the padding element: zero gradient, zero value, zero moments
+        assert float(buf[WRAP_N]) == 0.0
+
+
 @pytest.mark.gpu
 def test_native_adam_views_state_and_graph_capture(hip_lib):
     dev = torch.device("cuda:0")
