@@ -407,7 +407,9 @@ int nsff_fold_grads(const NsffFoldGradArgs* args, void* stream);
  *   g (n_rows, 256) [+ g2: a second summand, the fp16 rounding-remainder rows of a heads' job, or NULL], gb (n_rows) [+ gb2]
  *   d_w_head[r * ld_dhead + o] (+)= sum_i G[r][i] W_final[o][i] + gb[r] b_final[o]      d_b_head[r] (+)= gb[r]
  *   d_w_final[o][i] (+)= sum_r W_head[r * ld_head + o] G[r][i]                          d_b_final[o] (+)= sum_r W_head[r * ld_head + o] gb[r]
- * Two launches (rows of the head layer / neurons of *_final); fp32 FMAs in a fixed order: deterministic.  This is what ran
+ * Two launches (rows of the head layer / neurons of *_final); fp32 FMAs in a fixed order: deterministic.  Every pointer needs
+ * 4-byte alignment only, w_final included (the callers pass views of a flat parameter buffer without padding; off 16 bytes
+ * its rows are read float by float, the same products in the same order: the same bits).  This is what ran
  * through torch.addmm / `@` (rocBLAS) for view-direction models and for gradients returned as tensors until round 5.       */
 typedef struct NsffFoldDenseArgs {
     int32_t n_rows, accumulate;
