@@ -1198,6 +1198,59 @@ int     nsff_disparity_levels(int32_t H, int32_t W);
 int64_t nsff_disparity_dense_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
 int     nsff_disparity_dense(const NsffDisparityDenseArgs* args, void* stream);
 
+/* ---- disparity triangulated over several frames by chaining optical flow (csrc/parallax.hip; nsff_pl_amd/depth.py with span > 1;
+ * DESIGN.md section 11.5).  The measurement of `sparse` above sees the neighbours f +- 1 only: a slow camera's parallax per frame
+ * stays below min_parallax and nothing is measured, a fast camera's is measured against one frame's baseline.  Here a pixel is
+ * followed along the flow for up to `span` frames and votes against every baseline it reaches: the parallax grows with the number
+ * of frames k, a chained flow's noise like sqrt(k).  Entry points added without a change of NSFF_ABI_VERSION: nothing that existed
+ * changes.  The conventions and the common refusals of the section above hold (fp32, one fp32 operation per step in the order
+ * written, the file built -ffp-contract=off, compared bit for bit with numpy); ONE launch for all frames, both directions and all
+ * hops; no atomics on floats, no data-dependent loop, no synchronisation, no allocation: capturable.
+ *
+ * Frame f, direction d (0: s = +1 with flow_fw; 1: s = -1 with flow_bw), pixel p = (x, y), integers as floats.  Pm (F, 2, span, 12):
+ * row k - 1 of (f, d) is the row of `sparse` for the neighbour n = f + s * k (G = M_n M_f^-1, e = M_n (C_f - C_n)); twelve zeros: no
+ * vote (coincident centres; beyond the sequence ends the row is not read).
+ *   A_1 = flow_d[f][y][x]
+ *   alive_1 = known(A_1) && (valid == NULL || valid[f][d][p] != 0) && (masks == NULL || masks[f][p] != 0)
+ *             known: both components |.| <= 1e7, a NaN is not (as `sparse`)
+ *   for k = 1 .. span, n = f + s * k; the direction ends where n leaves 0 .. F-1:
+ *     vote  with (u, v) = A_k and the row Pm[f][d][k-1]: hx, hy, hz, up, vp, r, ax, ay, bx, by, p2, ab, aa exactly as `sparse`
+ *           states them (x, y the pixel's own coordinates in f);
+ *           vote = alive_k && row non-zero && hz > 0 && p2 >= min_parallax * min_parallax (fp32, formed on the host)
+ *           num += vote ? ab : 0;  den += vote ? aa : 0;  par += vote ? p2 : 0;  votes += vote
+ *           (a zero row has no vote, and the chain goes on)
+ *     hop   only if k < span and n + s is inside 0 .. F-1:  q = (up, vp), the same two floats as in the vote
+ *           inside = 0 <= qx <= W-1 && 0 <= qy <= H-1
+ *           b = flow_d[n] sampled bilinearly at q by the rule of nsff_motion_maps: x0 = floorf(qx), ax = qx - x0,
+ *               x1 = min(x0 + 1, W-1), y likewise, per component
+ *               b = ((B00 * (1 - ax) + B01 * ax) * (1 - ay)) + ((B10 * (1 - ax) + B11 * ax) * ay),  Bij = flow_d[n][yi][xj]
+ *           hop_ok = inside && all four taps known && (valid == NULL || the four taps of valid[n][d] != 0)
+ *                    && (masks == NULL || the four taps of masks[n] != 0)
+ *           alive_{k+1} = alive_k && hop_ok;  A_{k+1} = A_k + b, per component
+ *   The sums start from 0 and take d = 0 with k = 1 .. span, then d = 1 with k = 1 .. span: with span == 1 the order of `sparse`, and
+ *   the same bits.  Then, as there:  known = den > 0 && num > 0;  c = known ? par : 0;  n = known ? par * (num / den) : 0.
+ * The taps are read from q clamped into the image (the identity where q is inside, where alone a chain stays alive), so no
+ * address leaves a frame whatever the flow holds; what a dead chain goes on adding up is never used.
+ * valid (F, 2, H*W) uint8 and masks (F, H*W) uint8 (0 dynamic) are optional.  votes (F, H*W) uint8, optional: the votes of a pixel,
+ * at most 2 * span.  counts (F) int64, optional: the known pixels of each frame, an exact integer through the per-frame reduction;
+ * it needs `scratch`, nsff_disparity_span_scratch_bytes bytes, 16-byte aligned, ZERO before its first use and left zero.
+ * 1 <= span <= NSFF_DISPARITY_MAX_SPAN, n_frames <= 65535, 1 <= H * W < 2^31, min_parallax >= 0 (else NSFF_ERR_INVALID); flows and
+ * counts 8-byte, Pm, n, c and votes 4-byte aligned (NSFF_ERR_ALIGN) -- all before the launch.
+ * Bytes: per pixel and direction 10 for the first vote (flow, valid, mask) and 10 of unique taps per hop -- the 40 a lane issues
+ * per hop overlap between neighbouring pixels -- and 8 written (+1 with votes): about (20 * span + 9) bytes a pixel. */
+#define NSFF_DISPARITY_MAX_SPAN 8
+typedef struct NsffDisparitySpanArgs {
+    int32_t n_frames, H, W, span;              /* 1 <= span <= NSFF_DISPARITY_MAX_SPAN */
+    float   min_parallax;  int32_t pad_;
+    const float* flow_fw;  const float* flow_bw;     /* (F, H*W, 2)                          */
+    const float* Pm;                                 /* (F, 2, span, 12)                     */
+    const uint8_t* valid;  const uint8_t* masks;     /* optional, as nsff_disparity_sparse   */
+    float* n;  float* c;  uint8_t* votes;  int64_t* counts;   /* votes, counts optional      */
+    void* scratch;  int64_t scratch_bytes;
+} NsffDisparitySpanArgs;
+int64_t nsff_disparity_span_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int     nsff_disparity_span(const NsffDisparitySpanArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

@@ -282,6 +282,16 @@ class DisparityDenseArgs(C.Structure):
                 ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+DISPARITY_MAX_SPAN = 8                                                        # NSFF_DISPARITY_MAX_SPAN
+
+
+class DisparitySpanArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("span", C.c_int32),
+                ("min_parallax", C.c_float), ("pad_", C.c_int32),
+                ("flow_fw", _fp), ("flow_bw", _fp), ("Pm", _fp), ("valid", _fp), ("masks", _fp), ("n", _fp), ("c", _fp), ("votes", _fp),
+                ("counts", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
 RAY_RECORD = 16
 _DRAW_OUT =["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
@@ -440,6 +450,8 @@ _SIGNATURES = {
     "nsff_disparity_levels": (C.c_int, [C.c_int32, C.c_int32]),
     "nsff_disparity_dense_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_disparity_dense": (C.c_int, [C.POINTER(DisparityDenseArgs), _fp]),
+    "nsff_disparity_span_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_disparity_span": (C.c_int, [C.POINTER(DisparitySpanArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1668,6 +1680,44 @@ def disparity_sparse(flows_fw, flows_bw, Pm, valid=None, masks=None, min_paralla
     with torch.cuda.device(dev):
         _check(load().nsff_disparity_sparse(C.byref(a), _stream()), "nsff_disparity_sparse")
     return n, c
+
+
+def disparity_span_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_disparity_span_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def disparity_span(flows_fw, flows_bw, Pm, span, valid=None, masks=None, min_parallax=0.5, counts=None, votes=None, scratch=None,
+                   out=None):
+    """nsff_disparity_span (csrc/parallax.hip) on (F, H, W, 2) fp32 flows with the parallax rows Pm (F, 2, span, 12) fp32 of the
+    neighbours f +- 1 .. f +- span, valid (F, 2, H, W) uint8 and masks (F, H, W) uint8 optional -> (n, c, votes): n and c (F, H, W)
+    fp32 (the caller's pair ``out`` or fresh tensors), votes (F, H, W) uint8, the votes of each pixel (a fresh tensor when None).
+    counts (F,) int64: the known pixels of each frame.  scratch: a uint8 tensor of disparity_span_scratch_bytes() bytes, zero before
+    its first use (a fresh one when None)."""
+    require_gpu_tensor(flows_fw, "disparity_span: flows_fw")
+    F, H, W = (int(v) for v in flows_fw.shape[:3])
+    px, dev, span = F * H * W, flows_fw.device, int(span)
+    n, c = out if out is not None else (torch.empty(F, H, W, dtype=torch.float32, device=dev) for _ in range(2))
+    if votes is None:
+        votes = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    a = DisparitySpanArgs(n_frames=F, H=H, W=W, span=span, min_parallax=float(min_parallax))
+    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, px * 2), ("flow_bw", flows_bw, torch.float32, px * 2),
+                                   ("n", n, torch.float32, px), ("c", c, torch.float32, px),
+                                   ("Pm", Pm, torch.float32, F * 24 * span), ("valid", valid, torch.uint8, px * 2),
+                                   ("masks", masks, torch.uint8, px), ("votes", votes, torch.uint8, px),
+                                   ("counts", counts, torch.int64, F)):
+        if t is None:
+            continue
+        ptr = _dptr(t, dtype, f"disparity_span: {field}")
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"disparity_span: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        setattr(a, field, ptr)
+    if counts is not None and scratch is None:
+        scratch = torch.zeros(max(disparity_span_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    if scratch is not None:
+        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "disparity_span: scratch"), scratch.numel()
+    with torch.cuda.device(dev):
+        _check(load().nsff_disparity_span(C.byref(a), _stream()), "nsff_disparity_span")
+    return n, c, votes
 
 
 def _same_planes(who, first, **others):

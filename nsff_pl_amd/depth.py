@@ -1,5 +1,5 @@
 """Disparity maps from optical flow and camera poses, on the GPU (``nsff_disparity_sparse`` / ``nsff_disparity_dense``,
-csrc/depth.hip; there is no CPU path).
+csrc/depth.hip, and ``nsff_disparity_span``, csrc/parallax.hip; there is no CPU path).
 
 The reference takes its ``disps/*`` from DPT-large (preprocess.py:106-115), a network whose weights this project can neither ship
 nor run.  This module is a CLASSICAL STAND-IN, not DPT's disparity.  For a STATIC pixel, optical flow plus two camera poses is a
@@ -9,11 +9,20 @@ of disparity would move it.  Where there is no measurement (dynamic pixels, occl
 :func:`nsff_pl_amd.frames.resize_images` -> :func:`nsff_pl_amd.optflow.sequence_flows` -> :func:`nsff_pl_amd.motion.motion_masks`
 -> :func:`disparity_maps` -> ``RayBank.from_frames`` needs no network at all.
 
-* :func:`parallax_matrices` -- (F, 2, 12) fp32 on the host: per frame and direction, what turns a pixel and its flow into a disparity;
-* :func:`triangulate`       -- the measurement alone: ``{'sparse', 'conf', 'known', 'counts'}``;
+* :func:`parallax_matrices` -- (F, 2, 12) fp32 on the host: per frame and direction, what turns a pixel and its flow into a disparity
+  (``span`` > 1: (F, 2, span, 12), a row for each of the neighbours f +- 1 .. f +- span);
+* :func:`triangulate`       -- the measurement alone: ``{'sparse', 'conf', 'known', 'counts'}`` (``span`` > 1: and ``'votes'``);
 * :func:`densify`           -- the fill alone: (F, H, W) fp32 from a sparse map, its confidence and a guide image;
-* :func:`disparity_maps`    -- both: ``{'disps', 'sparse', 'conf', 'known', 'stats'}``;
-* :func:`sequence_geometry` -- flows, masks and disparities of a stack of frames in one call.
+* :func:`disparity_maps`    -- both: ``{'disps', 'sparse', 'conf', 'known', 'stats'}`` (``span`` > 1: and ``'votes'``);
+* :func:`sequence_geometry` -- flows, masks and disparities of a stack of frames in one call (``span=...`` goes to ``disparity_maps``).
+
+``span`` (1 .. ``_lib.DISPARITY_MAX_SPAN``; 1 is the default and the route described above, unchanged).  With ``span`` > 1 a pixel
+is followed along the flow -- its own flow to f +- 1, then the bilinearly sampled flow of f +- 1 at the place it landed, and so on
+-- for up to ``span`` frames each way, and is triangulated against every baseline it reaches in one least-squares vote
+(``nsff_disparity_span``, one launch).  The parallax grows with the number of frames k, the chained flow's noise only like sqrt(k).
+A chain ends for good at the first hop that leaves the image or lands on a tap whose flow is unknown, that fails the
+forward-backward check or that is dynamic: the masks at a hop are the same ``masks`` / ``valid`` arguments, read in the frame
+the chain has reached.
 
 Units.  ``disps`` is positive, larger is nearer, in the units of the poses it was given (1 / distance along the viewing axis): what
 ``scene.nearest_depth`` regresses against; the depth loss is shift- and scale-invariant anyway.  It goes unchanged into
@@ -23,7 +32,11 @@ Units.  ``disps`` is positive, larger is nearer, in the units of the poses it wa
 Known limit.  A dynamic pixel has no multi-view constraint.  Its disparity is filled in from its static surround, so a person in
 front of a wall gets roughly the wall's or the floor's disparity, not their own.  ``known`` and ``conf`` say where the map is
 measured and where it is filled.  Under near-pure camera rotation nothing is measured: coincident camera centres give a zero row
-and that direction has no vote.
+and that direction has no vote.  With ``span=1`` a slow camera measures nothing either: where the parallax between neighbouring
+frames stays below ``min_parallax`` most pixels are rejected and the map is filled in from almost nothing, or a frame comes out
+all zero (``stats.empty_frames``).  ``span`` > 1 is the cure as far as the sequence reaches: on the synthetic scene of the tests,
+rescaled so that one frame's parallax is too small, span 1 knows no static pixel and span 2 about 0.7 of them; with enough
+parallax span 3 has about two thirds of span 1's error.  A sequence shorter than ``span`` uses the baselines it has.
 """
 import numpy as np
 import torch
@@ -37,14 +50,22 @@ SMALL_BELOW = 512                             # tiles of TILE x TILE pixels in t
 GREY_SIGMA = 12.75                            # 0.05 of the 0..255 scale of optflow's grey stage
 
 
-def parallax_matrices(K, poses, rounded=True):
+def _check_span(who, span):
+    if isinstance(span, bool) or not isinstance(span, (int, np.integer)) or not 1 <= span <= _lib.DISPARITY_MAX_SPAN:
+        raise ValueError(f"{who}: span must be an integer from 1 to {_lib.DISPARITY_MAX_SPAN}, got {span!r}")
+    return int(span)
+
+
+def parallax_matrices(K, poses, rounded=True, span=1):
     """(F, 2, 12): per frame f and direction d (0: the neighbour n = f + 1, 1: n = f - 1) the nine entries of ``M_n M_f^-1``, row-major,
     and the three of ``e = M_n (C_f - C_n)``.  K (3,3) or (1,3,3); poses (F,3,4) camera-to-world.  From the world -> pixel convention
     of :func:`nsff_pl_amd.frames.projection_matrices`, with ``M = K diag(1,-1,-1) R^-1`` and the camera centre C: a pixel
     ``x = (u, v, 1)`` of f at depth ``1 / delta`` appears in n at ``delta e + h``, ``h = M_n M_f^-1 x``.  float64 throughout, rounded
     once to fp32 (``rounded=False`` returns the float64 values); NOT normalised, because e carries the units of the poses.  A row is
     all zeros where there is no neighbour (the sequence ends) and where the two camera centres coincide
-    (:data:`nsff_pl_amd.motion.COINCIDENT`'s rule): the kernel reads a zero row as "no vote"."""
+    (:data:`nsff_pl_amd.motion.COINCIDENT`'s rule): the kernel reads a zero row as "no vote".  ``span`` > 1: (F, 2, span, 12), row
+    k - 1 built for the neighbour n = f + k / f - k by the same formula and the same rules."""
+    span = _check_span("parallax_matrices", span)
     K, poses = motion._host(K), motion._host(poses)
     if K.shape == (1, 3, 3):
         K = K[0]
@@ -56,17 +77,21 @@ def parallax_matrices(K, poses, rounded=True):
     M = K @ np.diag([1.0, -1.0, -1.0]) @ np.linalg.inv(poses[:, :, :3])
     M_inv = np.linalg.inv(M)
     C = poses[:, :, 3]
-    out = np.zeros((F, 2, 12))
+    out = np.zeros((F, 2, span, 12))
     for f in range(F):
-        for d, n in enumerate((f + 1, f - 1)):
-            if not 0 <= n < F:
-                continue
-            base = C[f] - C[n]
-            if np.linalg.norm(base) <= motion.COINCIDENT * max(1.0, np.linalg.norm(C[f]), np.linalg.norm(C[n])):
-                continue
-            row = np.concatenate([(M[n] @ M_inv[f]).ravel(), M[n] @ base])
-            if np.isfinite(row).all():
-                out[f, d] = row
+        for d, step in enumerate((+1, -1)):
+            for k in range(1, span + 1):
+                n = f + step * k
+                if not 0 <= n < F:
+                    break
+                base = C[f] - C[n]
+                if np.linalg.norm(base) <= motion.COINCIDENT * max(1.0, np.linalg.norm(C[f]), np.linalg.norm(C[n])):
+                    continue
+                row = np.concatenate([(M[n] @ M_inv[f]).ravel(), M[n] @ base])
+                if np.isfinite(row).all():
+                    out[f, d, k - 1] = row
+    if span == 1:
+        out = out[:, :, 0]
     return torch.tensor(out, dtype=torch.float32) if rounded else out
 
 
@@ -101,7 +126,7 @@ def _check_parallax(who, min_parallax):
         raise ValueError(f"{who}: min_parallax must be a finite number >= 0, got {min_parallax}")
 
 
-def triangulate(flows_fw, flows_bw, K, poses, valid=None, masks=None, min_parallax=0.5, scratch=None):
+def triangulate(flows_fw, flows_bw, K, poses, valid=None, masks=None, min_parallax=0.5, scratch=None, span=1):
     """The disparity of the static pixels of F frames by motion parallax; one launch, everything stays on the GPU.
 
     flows_fw / flows_bw (F, H, W, 2) fp32 pixels on the GPU (unknown flow: ``|.| > 1e7``); K (3,3); poses (F,3,4) camera-to-world;
@@ -115,28 +140,40 @@ def triangulate(flows_fw, flows_bw, K, poses, valid=None, masks=None, min_parall
     * ``'known'``  (F, H, W) bool;
     * ``'counts'`` (F,) int64 on the GPU: the known pixels of each frame.
 
-    ``scratch``: a uint8 tensor of ``_lib.disparity_sparse_scratch_bytes(F, H, W)`` bytes, zero before its first use and left zero
-    (a fresh one when None)."""
-    out = _triangulate("triangulate", flows_fw, flows_bw, K, poses, valid, masks, min_parallax, scratch)
+    ``span`` (1 .. ``_lib.DISPARITY_MAX_SPAN``): 1 measures against the neighbours f +- 1 alone (``nsff_disparity_sparse``); more
+    follows every pixel along the flow for up to ``span`` frames each way and lets it vote against every baseline it reaches
+    (``nsff_disparity_span``; the module text says how a chain ends), and adds
+
+    * ``'votes'`` (F, H, W) uint8: the votes of each pixel, at most 2 ``span``.
+
+    ``scratch``: a uint8 tensor of ``_lib.disparity_sparse_scratch_bytes(F, H, W)`` bytes (the same size for every span), zero
+    before its first use and left zero (a fresh one when None)."""
+    out = _triangulate("triangulate", flows_fw, flows_bw, K, poses, valid, masks, min_parallax, scratch, span)
     del out["n"]
     return out
 
 
-def _triangulate(who, flows_fw, flows_bw, K, poses, valid, masks, min_parallax, scratch):
+def _triangulate(who, flows_fw, flows_bw, K, poses, valid, masks, min_parallax, scratch, span=1):
     _check_parallax(who, min_parallax)
+    span = _check_span(who, span)
     flows_fw, flows_bw = motion._flows(flows_fw, flows_bw, who)
     F, H, W = (int(v) for v in flows_fw.shape[:3])
     dev = flows_fw.device
-    Pm = parallax_matrices(K, poses)
+    Pm = parallax_matrices(K, poses, span=span)
     if Pm.shape[0] != F:
         raise RuntimeError(f"{who}: {F} frames of flow need {F} poses, got {Pm.shape[0]}")
     valid = _uint8_maps(valid, (F, 2, H, W), dev, who, "valid")
     masks = _uint8_maps(masks, (F, H, W), dev, who, "masks")
     counts = torch.empty(F, dtype=torch.int64, device=dev)
-    n, c = _lib.disparity_sparse(flows_fw, flows_bw, Pm.to(dev), valid=valid, masks=masks, min_parallax=min_parallax, counts=counts,
-                                 scratch=scratch)
+    extra = {}
+    if span == 1:
+        n, c = _lib.disparity_sparse(flows_fw, flows_bw, Pm.to(dev), valid=valid, masks=masks, min_parallax=min_parallax, counts=counts,
+                                     scratch=scratch)
+    else:
+        n, c, extra["votes"] = _lib.disparity_span(flows_fw, flows_bw, Pm.to(dev), span, valid=valid, masks=masks,
+                                                   min_parallax=min_parallax, counts=counts, scratch=scratch)
     known = c > 0
-    return dict(sparse=torch.where(known, n / c, torch.zeros_like(n)), conf=c, known=known, counts=counts, n=n)
+    return dict(sparse=torch.where(known, n / c, torch.zeros_like(n)), conf=c, known=known, counts=counts, n=n, **extra)
 
 
 def default_route(n_frames, H, W):
@@ -233,7 +270,7 @@ class DisparityStats:
 
 
 def disparity_maps(images, flows_fw, flows_bw, K, poses, masks=None, valid=None, min_parallax=0.5, levels=3, iters=30, lam=8.0,
-                   sigma=GREY_SIGMA, fused=None, scratch=None):
+                   sigma=GREY_SIGMA, fused=None, scratch=None, span=1):
     """Disparity maps of F frames from their optical flow and camera poses: :func:`triangulate`, then :func:`densify` guided by
     ``images`` ((F, H, W, 3) uint8 frames or an (F, H, W) fp32 guide); everything stays on the GPU.  Returns a dict:
 
@@ -245,23 +282,28 @@ def disparity_maps(images, flows_fw, flows_bw, K, poses, masks=None, valid=None,
     every pixel counts as static and a moving object gets a wrong disparity of its own instead of its surround's.  The parameters
     are starting values that nobody has tuned on real data (see :func:`densify`).  A frame with no known pixel -- a single frame, a
     sequence shot from one spot, flows that all fail the check -- comes out ALL ZERO: ``stats.known_fraction`` / ``stats.empty_frames``
-    detect it.  ``scratch`` as for :func:`densify`.  See the module text for the units and the method's known limit."""
+    detect it.  ``span`` as for :func:`triangulate`: more than 1 measures over several frames by chained flow -- the cure for a slow
+    camera -- and adds ``'votes'``.  ``scratch`` as for :func:`densify`.  See the module text for the units and the method's known
+    limit."""
     who = "disparity_maps"
     _check_dense(who, levels, iters, lam, sigma)
-    tri = _triangulate(who, flows_fw, flows_bw, K, poses, valid, masks, min_parallax, None)
+    tri = _triangulate(who, flows_fw, flows_bw, K, poses, valid, masks, min_parallax, None, span)
     n = tri.pop("n")
     F, H, W = (int(v) for v in n.shape)
     disps = _densify(who, n, tri["conf"], images, levels, iters, lam, sigma, fused, scratch)
-    return dict(disps=disps, sparse=tri["sparse"], conf=tri["conf"], known=tri["known"], stats=DisparityStats(tri["counts"], H * W))
+    extra = {"votes": tri["votes"]} if "votes" in tri else {}
+    return dict(disps=disps, sparse=tri["sparse"], conf=tri["conf"], known=tri["known"], stats=DisparityStats(tri["counts"], H * W), **extra)
 
 
 def sequence_geometry(images, K, poses, flow_kw=None, mask_kw=None, **disparity_kw):
     """images (F, H, W, 3) uint8 + K + poses -> ``{'disps', 'masks', 'flows_fw', 'flows_bw', 'valid', 'known', 'conf', 'stats',
     'motion_stats'}``: :func:`nsff_pl_amd.optflow.sequence_flows` -> :func:`nsff_pl_amd.motion.motion_masks` ->
     :func:`disparity_maps`, what ``RayBank.from_frames(K, poses, images, disps, masks, flows_fw, flows_bw)`` takes besides the
-    frames.  ``flow_kw`` / ``mask_kw`` go to the first two, ``**disparity_kw`` to the last."""
+    frames.  ``flow_kw`` / ``mask_kw`` go to the first two, ``**disparity_kw`` (``span=...`` among them; then ``'votes'`` is returned
+    too) to the last."""
     flows = optflow.sequence_flows(images, check=False, **(flow_kw or {}))
     mm = motion.motion_masks(flows["flows_fw"], flows["flows_bw"], K, poses, **(mask_kw or {}))
     out = disparity_maps(images, flows["flows_fw"], flows["flows_bw"], K, poses, masks=mm["mask"], valid=mm["valid"], **disparity_kw)
+    extra = {"votes": out["votes"]} if "votes" in out else {}
     return dict(disps=out["disps"], masks=mm["mask"], flows_fw=flows["flows_fw"], flows_bw=flows["flows_bw"], valid=mm["valid"],
-                known=out["known"], conf=out["conf"], stats=out["stats"], motion_stats=mm["stats"])
+                known=out["known"], conf=out["conf"], stats=out["stats"], motion_stats=mm["stats"], **extra)

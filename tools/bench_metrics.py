@@ -58,6 +58,10 @@ writes d, 20 B per pixel, whether it runs one iteration or k: `relax30_*_bound_u
 ((T + 2 k) / T)^2), the whole nsff_disparity_dense call on each route, and depth.disparity_maps with its default route (host-side
 parallax rows, their upload, the grey stage and the allocations included).  --only disparity_resources needs no GPU: the
 compiler's report of VGPRs, scratch, LDS and waves per SIMD of every kernel of csrc/depth.hip.
+On F = 30 frames also nsff_disparity_span (csrc/parallax.hip) at span 1, 2, 4 and 8 with valid, masks, votes and counts, and
+nsff_disparity_sparse on the same inputs, all five taken in turn: `span{S}_us` against `span{S}_bound_us`, the (20 S + 9) B per pixel
+it must move at the HBM peak (per direction 10 B for the first vote and 10 B of unique taps per hop; 9 B written), and
+`span{S}_bound_fraction`, the bound over the time; `span1_sparse_us` is the one-frame kernel beside span 1.
 """
 import argparse
 import json
@@ -510,8 +514,45 @@ def bench_disparity(dev, g, W, H, reps, F, iters=30):
     calls = time_alternating_us([lambda kw=kw: _lib.disparity_dense(n, c, grey, disps, iters=iters, scratch=scratch, **kw) for _, kw in routes], reps)
     for (name, _), t in zip(routes, calls):
         out[f"{tag}_dense_{name}_us"] = t
+    if F > 1:
+        out.update(bench_disparity_span(dev, fw, bw, K, poses, valid, masks, reps, tag))
     poses_F = poses[:F] if F > 1 else poses[:1]
     out[f"{tag}_maps_call_default_us"] = time_us(lambda: depth.disparity_maps(rgb, fw, bw, K, poses_F, masks=masks, valid=valid), reps)
+    return out
+
+
+DISPARITY_SPANS = (1, 2, 4, 8)
+
+
+def disparity_span_bytes_per_pixel(span):
+    """What nsff_disparity_span must move: per direction 10 B for the first vote (flow, valid, mask) and 10 B of unique taps per
+    hop, n, c and votes written."""
+    return 20 * span + 9
+
+
+def bench_disparity_span(dev, fw, bw, K, poses, valid, masks, reps, tag):
+    """nsff_disparity_span at every span of DISPARITY_SPANS and nsff_disparity_sparse on the same inputs, taken in turn."""
+    from nsff_pl_amd import depth
+    F, H, W = (int(v) for v in fw.shape[:3])
+    px = F * H * W
+    counts = torch.empty(F, dtype=torch.int64, device=dev)
+    votes = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    out2 = tuple(torch.empty(F, H, W, device=dev) for _ in range(2))
+    scratch = torch.zeros(_lib.disparity_span_scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    rows = {s: depth.parallax_matrices(K, poses, span=s)[:F].reshape(F, 2, s, 12).contiguous().to(dev) for s in DISPARITY_SPANS}
+    fns = [lambda s=s: _lib.disparity_span(fw, bw, rows[s], s, valid=valid, masks=masks, counts=counts, votes=votes, scratch=scratch, out=out2)
+           for s in DISPARITY_SPANS]
+    Pm1 = rows[1].reshape(F, 2, 12)
+    fns.append(lambda: _lib.disparity_sparse(fw, bw, Pm1, valid=valid, masks=masks, counts=counts, scratch=scratch))
+    times = time_alternating_us(fns, reps)
+    out = {}
+    for s, t in zip(DISPARITY_SPANS, times):
+        fns[DISPARITY_SPANS.index(s)]()
+        bound = px * disparity_span_bytes_per_pixel(s) / HBM_PEAK * 1e6
+        out[f"{tag}_span{s}_us"], out[f"{tag}_span{s}_bound_us"], out[f"{tag}_span{s}_bound_fraction"] = t, bound, bound / t
+        out[f"{tag}_span{s}_known_fraction"] = float(counts.sum()) / px
+        out[f"{tag}_span{s}_mean_votes"] = float(votes.sum(dtype=torch.int64)) / px
+    out[f"{tag}_span1_sparse_us"] = times[-1]
     return out
 
 
