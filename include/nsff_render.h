@@ -1108,6 +1108,41 @@ int     nsff_optflow_levels(int32_t H, int32_t W, int32_t levels);
 int64_t nsff_optflow_scratch_bytes(int32_t n_pairs, int32_t H, int32_t W, int32_t levels);
 int     nsff_optflow(const NsffOptflowArgs* args, void* stream);
 
+/* ---- the image-guided weighted median of a flow map (csrc/flowmedian.hip; nsff_pl_amd/optflow.py refine_flow; DESIGN.md section
+ * 11.4): the non-local term of "Classic+NL" (Sun, Roth and Black 2010) as one filter pass over the flow of P pairs.  TV-L1 rounds a
+ * motion edge off; the weighted median ties it to the image edge it belongs to.  Entry point added without a change of
+ * NSFF_ABI_VERSION: nothing that existed changes.  The conventions of the section above hold (fp32, one fp32 operation per step in
+ * the order written, the file built -ffp-contract=off, IEEE division).
+ *
+ * flow (P, H*W, 2) fp32; grey (P, H*W) fp32, finite, on the 0..255 scale: the grey stage of the image the flow STARTS from; valid
+ * (P, H*W) uint8, optional; out (P, H*W, 2) fp32, which must not overlap flow.  Pixel p, with known(f) = both components |.| <= 1e7
+ * (a NaN is not; the rule of nsff_motion_maps):
+ *   unknown centre   !known(flow[p]):  out[p] = flow[p], bits unchanged.
+ *   candidates       q = p + (dx, dy), |dx|, |dy| <= radius, with q inside the image (there is no replicated border),
+ *                    known(flow[q]) and (q == p || valid == NULL || valid[q] != 0).
+ *   weight           di = (grey[q] - grey[p]) / sigma_i;  w = 1f / ((1f + di * di) * s[dy][dx]);  wq = (int) rintf(w * 65535f)
+ *                    s[dy][dx] = 1 + (dx^2 + dy^2) / sigma_s^2, formed on the host in double from the fp32 sigma_s and rounded once;
+ *                    the centre has wq = 65535, so the total is never zero.  The weights are INTEGERS of 16 bits on purpose: every
+ *                    sum is exact whatever its order, and the result the same for any selection algorithm.
+ *   result           per component c:  out[p][c] = the smallest candidate value v with
+ *                    2 * sum{wq_j : flow[q_j][c] <= v} >= sum{wq_j}.  Values compare as numbers: -0 and +0 are one value (+0 comes back).
+ * tiled == 0: one thread per pixel reads global memory and bisects the order-preserving 32-bit key of the value in 32 steps, the
+ * weights formed again on every visit: the definition.  tiled == 1: a 32 x 8 tile with its halo in LDS, a pixel's integer weights
+ * computed once and kept in registers two to a word; bit-identical to the plain route, built for every radius.
+ * NSFF_FLOW_MEDIAN_TILED is the measured default.  ONE launch for all pairs; fixed trip counts, no atomics, no data-dependent loop,
+ * no synchronisation, no allocation: capturable.
+ * 1 <= radius <= NSFF_FLOW_MEDIAN_MAX_RADIUS; sigma_i, sigma_s > 0 and finite; 1 <= P <= 65535; 1 <= H, W <= 32768; P * H * W < 2^31;
+ * tiled 0 or 1; out overlapping flow: NSFF_ERR_INVALID.  A missing flow / grey / out NSFF_ERR_NULL.  flow and out 8-byte, grey 4-byte
+ * aligned (NSFF_ERR_ALIGN).  All before the launch. */
+#define NSFF_FLOW_MEDIAN_MAX_RADIUS 7
+#define NSFF_FLOW_MEDIAN_TILED      1   /* the route nsff_pl_amd.optflow.refine_flow takes when not told */
+typedef struct NsffFlowMedianArgs {
+    int32_t n_pairs, H, W, radius;
+    float   sigma_i, sigma_s;  int32_t tiled, pad_;
+    const float* flow;  const float* grey;  const uint8_t* valid;  float* out;
+} NsffFlowMedianArgs;
+int     nsff_flow_median(const NsffFlowMedianArgs* args, void* stream);
+
 /* ---- disparity from optical flow and camera poses (csrc/depth.hip; nsff_pl_amd/depth.py): the classical
  * stand-in for the reference's DPT step (preprocess.py:106-115).  For a static pixel flow plus two poses is a depth measurement
  * (motion parallax); where there is none an image-guided fill gives a dense map.  Entry points added without a change of

@@ -22,7 +22,7 @@ from .tracks import advect, draw
 from . import motion
 from .motion import motion_masks, flow_consistency, fundamental_matrices
 from . import optflow
-from .optflow import optical_flow, sequence_flows
+from .optflow import optical_flow, sequence_flows, refine_flow
 from . import depth
 from .depth import disparity_maps, triangulate, densify, parallax_matrices, sequence_geometry
 from . import panels
@@ -38,7 +38,7 @@ __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "
            "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
            "tracks", "advect", "draw",
            "motion", "motion_masks", "flow_consistency", "fundamental_matrices",
-           "optflow", "optical_flow", "sequence_flows",
+           "optflow", "optical_flow", "sequence_flows", "refine_flow",
            "depth", "disparity_maps", "triangulate", "densify", "parallax_matrices", "sequence_geometry",
            "panels", "validation_panels", "error_blend", "LPIPS",
            "scene", "nearest_depth", "scene_from_colmap", "visibility_matrix"]

@@ -292,6 +292,15 @@ class DisparitySpanArgs(C.Structure):
                 ("counts", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
 
+FLOW_MEDIAN_MAX_RADIUS, FLOW_MEDIAN_TILED = 7, 1                              # NSFF_FLOW_MEDIAN_*
+
+
+class FlowMedianArgs(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("radius", C.c_int32),
+                ("sigma_i", C.c_float), ("sigma_s", C.c_float), ("tiled", C.c_int32), ("pad_", C.c_int32),
+                ("flow", _fp), ("grey", _fp), ("valid", _fp), ("out", _fp)]
+
+
 RAY_RECORD = 16
 _DRAW_OUT =["rays", "rgbs", "ts", "cam_ids", "disps", "rays_mask", "uv_fw", "uv_bw", "rand_idx"]
 
@@ -452,6 +461,7 @@ _SIGNATURES = {
     "nsff_disparity_dense": (C.c_int, [C.POINTER(DisparityDenseArgs), _fp]),
     "nsff_disparity_span_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_disparity_span": (C.c_int, [C.POINTER(DisparitySpanArgs), _fp]),
+    "nsff_flow_median": (C.c_int, [C.POINTER(FlowMedianArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
     "nsff_prof_enable": (C.c_int, [C.c_int]),
@@ -1648,6 +1658,28 @@ def optflow(images0, images1, flow, levels=5, warps=5, iters=30, lam=0.15, theta
     with torch.cuda.device(dev):
         _check(load().nsff_optflow(C.byref(a), _stream()), "nsff_optflow")
     return flow
+
+
+def flow_median(flow, grey, out, valid=None, radius=7, sigma_i=12.75, sigma_s=7.0, tiled=True):
+    """nsff_flow_median (csrc/flowmedian.hip): out (P, H, W, 2) fp32 = the image-guided weighted median of flow (P, H, W, 2) fp32 with
+    the guide grey (P, H, W) fp32 and valid (P, H, W) uint8 optional; out must not overlap flow."""
+    require_gpu_tensor(flow, "flow_median: flow")
+    if flow.dim() != 4 or flow.shape[-1] != 2:
+        raise RuntimeError(f"flow_median: flow: need (P, H, W, 2), got {tuple(flow.shape)}")
+    P, H, W = (int(v) for v in flow.shape[:3])
+    px, dev = P * H * W, flow.device
+    a = FlowMedianArgs(n_pairs=P, H=H, W=W, radius=int(radius), sigma_i=float(sigma_i), sigma_s=float(sigma_s), tiled=int(bool(tiled)))
+    for field, t, dtype, numel in (("flow", flow, torch.float32, px * 2), ("grey", grey, torch.float32, px),
+                                   ("valid", valid, torch.uint8, px), ("out", out, torch.float32, px * 2)):
+        if t is None:
+            continue
+        ptr = _dptr(t, dtype, f"flow_median: {field}")
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"flow_median: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        setattr(a, field, ptr)
+    with torch.cuda.device(dev):
+        _check(load().nsff_flow_median(C.byref(a), _stream()), "nsff_flow_median")
+    return out
 
 
 # ---- disparity from flow and poses (csrc/depth.hip).  Planes are contiguous fp32 (F, H, W) GPU tensors.

@@ -62,6 +62,10 @@ On F = 30 frames also nsff_disparity_span (csrc/parallax.hip) at span 1, 2, 4 an
 nsff_disparity_sparse on the same inputs, all five taken in turn: `span{S}_us` against `span{S}_bound_us`, the (20 S + 9) B per pixel
 it must move at the HBM peak (per direction 10 B for the first vote and 10 B of unique taps per hop; 9 B written), and
 `span{S}_bound_fraction`, the bound over the time; `span1_sparse_us` is the one-frame kernel beside span 1.
+The image-guided weighted median of a flow map (--only flowmedian; csrc/flowmedian.hip) at 512 x 288 on P = 1 and P = 58 pairs, radius 3
+and radius 7, default weights, with `valid`: nsff_flow_median alone on preallocated tensors, the plain and the tiled route taken in
+turn, the median of 30 (device events).  `visits` is what the selection must do whatever the route, 2 components x 32 steps x
+(2 r + 1)^2 candidates a pixel, and `*_visits_per_ns` that count over the time.  No target time: nothing comparable was measured before.
 """
 import argparse
 import json
@@ -473,6 +477,30 @@ def bench_optflow(dev, g, W, H, reps, P, iters=30):
     return out
 
 
+def bench_flowmedian(dev, g, W, H, P, reps=30):
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    # two motions with an image edge on the motion edge, a rounded flow edge, noise, and a check that fails near the edge
+    dist = torch.hypot(xs - 0.5 * W, ys - 0.5 * H) - 0.22 * W
+    disc = dist <= 0
+    grey = (torch.where(disc, 200.0, 80.0) + 25 * torch.sin(0.31 * xs + 0.12 * ys)).expand(P, H, W).contiguous()
+    grey = grey + 2 * torch.randn(P, H, W, device=dev, generator=g)
+    blend = torch.sigmoid(-dist / 3)[..., None]
+    flow = (blend * torch.tensor([3.0, -1.5], device=dev) + (1 - blend) * torch.tensor([-2.0, 0.7], device=dev)).expand(P, H, W, 2).contiguous()
+    flow = flow + 0.05 * torch.randn(P, H, W, 2, device=dev, generator=g)
+    valid = ((dist.abs() > 3) & (torch.rand(P, H, W, device=dev, generator=g) < 0.97)).to(torch.uint8).contiguous()
+    out_t = torch.empty_like(flow)
+    out = {}
+    for r in (3, 7):
+        fns = [lambda t=t, r=r: _lib.flow_median(flow, grey, out_t, valid=valid, radius=r, tiled=t) for t in (False, True)]
+        times = time_alternating_us(fns, reps, warmup=3)
+        visits = 2 * 32 * (2 * r + 1) ** 2 * P * H * W
+        for name, t in zip(("plain", "tiled"), times):
+            out[f"flowmedian_P{P}_r{r}_{name}_us"] = t
+            out[f"flowmedian_P{P}_r{r}_{name}_visits_per_ns"] = visits / (t * 1e3)
+        out[f"flowmedian_P{P}_r{r}_plain_over_tiled"] = times[0] / times[1]
+    return out
+
+
 DISPARITY_SPARSE_BYTES_PER_PIXEL = 8 + 8 + 2 + 1 + 4 + 4     # both flows, valid of both directions, the mask in; n and c out
 DISPARITY_RELAX_BYTES_PER_PIXEL = (4 + 1) * 4                # one launch of the relaxation: d, n, c, grey in, d out
 
@@ -584,7 +612,7 @@ def disparity_resources():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion, optflow, disparity (default: everything but lpips, optflow and disparity); disparity_resources alone needs no GPU")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion, optflow, flowmedian, disparity (default: everything but lpips, optflow, flowmedian and disparity); disparity_resources alone needs no GPU")
     args = ap.parse_args()
     if args.only == "disparity_resources":
         print(json.dumps(disparity_resources()))
@@ -625,6 +653,10 @@ def main():
         if "optflow" in only:
             for P in (1, 58):
                 out.update(bench_optflow(dev, g, W, H, args.reps, P))
+                torch.cuda.empty_cache()
+        if "flowmedian" in only:
+            for P in (1, 58):
+                out.update(bench_flowmedian(dev, g, W, H, P))
                 torch.cuda.empty_cache()
         if "disparity" in only:
             for F in (1, 30):
