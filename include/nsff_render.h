@@ -1286,6 +1286,88 @@ typedef struct NsffDisparitySpanArgs {
 int64_t nsff_disparity_span_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
 int     nsff_disparity_span(const NsffDisparitySpanArgs* args, void* stream);
 
+/* ---- motion masks over several frames: the chained epipolar test and the propagation of "dynamic" along the flow
+ * (csrc/motionspan.hip; nsff_pl_amd/motion.py with span > 1 / reach > 0).  nsff_motion_maps tests a pixel's
+ * flow against the neighbours f +- 1 only: an object that drifts less than `threshold` a frame off its epipolar line is never
+ * flagged, and an object that pauses is static in the frames of the pause.  nsff_motion_span follows a pixel along the flow for up
+ * to `span` frames and tests it against every line it reaches; nsff_mask_propagate carries "dynamic" from the frames f +- 1 ..
+ * f +- reach back along the same chain.  Entry points added without a change of NSFF_ABI_VERSION: nothing that existed changes.
+ * The conventions of nsff_disparity_span hold (fp32, one fp32 operation per step in the order written, IEEE division and square
+ * root, the file built -ffp-contract=off, compared bit for bit with numpy); ONE launch each for all frames, both directions and
+ * all hops; no atomics on floats, no data-dependent loop beyond the fixed hop count, no synchronisation, no allocation: capturable.
+ * known(w): both components |.| <= 1e7, a NaN is not (nsff_motion_maps' rule).  UNKNOWN = NSFF_FLOW_UNKNOWN = 1e10.
+ *
+ * nsff_motion_span.  flow_fw, flow_bw (F, H*W, 2).  Fm (F, 2, span, 3, 3): row k - 1 of (f, d) maps a pixel of f to its line in
+ * f + k (d = 0) / f - k (d = 1); a zero matrix beyond the sequence ends and for coincident centres.  valid (F, 2, H*W) uint8,
+ * optional.  hop_scale (span).  Frame f, direction d (0: s = +1 with A = flow_fw; 1: s = -1 with A = flow_bw), pixel p = (x, y),
+ * integers as floats:
+ *   alive = known(A[f][p]) && (valid == NULL || valid[f][d][p] != 0);  (u, v) = A[f][p];  best = 0;  hops = 0
+ *   for k = 1 .. span, nb = f + s * k; the direction ends where nb leaves 0 .. F-1:
+ *     q = (x + u, y + v)
+ *     with M = Fm[f][d][k-1]:  l_i = (M[i][0] x + M[i][1] y) + M[i][2],  r = (l0 qx + l1 qy) + l2,  n = l0 l0 + l1 l1,
+ *       e = |r| / sqrtf(n)                                                   (exactly as nsff_motion_maps forms them)
+ *     if alive && isfinite(n) && n > 0:  best = fmaxf(best, e * hop_scale[k-1]);  hops += 1
+ *     hop, only if k < span and nb + s is inside 0 .. F-1:
+ *       inside = 0 <= qx <= W-1 && 0 <= qy <= H-1
+ *       b = flow_d[nb] sampled bilinearly at q by the rule of nsff_motion_maps: x0 = floorf(qx), ax = qx - x0,
+ *           x1 = min(x0 + 1, W-1), y likewise, per component
+ *           b = ((B00 * (1 - ax) + B01 * ax) * (1 - ay)) + ((B10 * (1 - ax) + B11 * ax) * ay),  Bij = flow_d[nb][yi][xj]
+ *       hop_ok = inside && all four taps known && (valid == NULL || the four taps of valid[nb][d] != 0)
+ *                (the hop of nsff_disparity_span; there is no mask test here)
+ *       alive = alive && hop_ok;  (u, v) = (u + b_u, v + b_v)
+ *   err[f][d][p] = hops ? best : UNKNOWN;  hops[f][d][p] = hops;  over_d = hops > 0 && best > threshold
+ *   raw[f][p] = over_fw || over_bw ? 0 : 255                                 (the reference's polarity: 0 dynamic)
+ * err (F, 2, H*W) fp32 and hops (F, 2, H*W) uint8 are optional; raw (F, H*W) uint8 is not.  counts (F, 3) int64, optional:
+ * [over fw, over bw, dynamic pixels of raw], exact integers through the per-frame reduction; it needs `scratch`,
+ * nsff_motion_span_scratch_bytes bytes, 16-byte aligned, ZERO before its first use and left zero.  With span == 1, hop_scale = {1}
+ * and nsff_motion_maps' own `valid`, raw and the over-counts are nsff_motion_maps'.
+ * The taps are read from q clamped into the image (the identity where q is inside, where alone a chain stays alive), so no
+ * address leaves a frame whatever the flow holds; what a dead chain goes on adding up is never used.
+ * 1 <= span <= NSFF_MOTION_MAX_SPAN, n_frames <= 65535, 1 <= H * W < 2^31, threshold >= 0, scratch_bytes large enough (else
+ * NSFF_ERR_INVALID); flow_fw, flow_bw, Fm, hop_scale, raw, and scratch with counts, not NULL (NSFF_ERR_NULL); scratch 16-byte,
+ * flows and counts 8-byte, Fm, hop_scale and err 4-byte aligned (NSFF_ERR_ALIGN) -- all before the launch.
+ * Bytes: per pixel and direction 9 for the first step (flow, valid) and 10 of unique taps per hop, and 11 written a pixel (err,
+ * hops, raw): about (20 * span + 9) a pixel.
+ *
+ * nsff_mask_propagate.  src (F, H*W) uint8, 0 = dynamic; flows and valid as above.  Per pixel and direction alive and (u, v) start
+ * as above, hits = 0:
+ *   for k = 1 .. reach, nb = f + s * k; the direction ends where nb leaves 0 .. F-1:
+ *     q = (x + u, y + v);  inside = 0 <= qx <= W-1 && 0 <= qy <= H-1
+ *     xi = (int)rintf(qx), yi = (int)rintf(qy)         (round half to even, numpy's rint; used only where inside)
+ *     if alive && inside && src[nb][yi][xi] == 0:  hits += 1
+ *     hop exactly as above (k < reach, nb + s inside 0 .. F-1)
+ *   dst[f][p] = (src[f][p] == 0 || hits_fw + hits_bw > 0) ? 0 : src[f][p]
+ * hits (F, H*W) uint8, optional: hits_fw + hits_bw, at most 2 * reach.  zero_counts (F) int64, optional: the zero pixels of each
+ * frame of dst, with the same scratch rule (nsff_motion_span_scratch_bytes covers both calls).
+ * 1 <= reach <= NSFF_PROPAGATE_MAX_REACH, the frame limits above, dst must not overlap src, scratch_bytes large enough (else
+ * NSFF_ERR_INVALID); src, dst, flow_fw, flow_bw, and scratch with zero_counts, not NULL (NSFF_ERR_NULL); scratch 16-byte, flows and
+ * zero_counts 8-byte aligned (NSFF_ERR_ALIGN) -- all before the launch.
+ * Bytes: per pixel and direction 9 for the first step, 1 of mask per step and 10 of unique taps per hop; 2 read and written a
+ * pixel (src, dst; +1 with hits): (22 * reach + 1) a pixel with hits. */
+#define NSFF_MOTION_MAX_SPAN 8
+#define NSFF_PROPAGATE_MAX_REACH 8
+typedef struct NsffMotionSpanArgs {
+    int32_t n_frames, H, W, span;              /* 1 <= span <= NSFF_MOTION_MAX_SPAN */
+    float   threshold;  int32_t pad_;
+    const float* flow_fw;  const float* flow_bw;     /* (F, H*W, 2)                          */
+    const float* Fm;                                 /* (F, 2, span, 3, 3)                   */
+    const float* hop_scale;                          /* (span)                               */
+    const uint8_t* valid;                            /* (F, 2, H*W), optional                */
+    float* err;  uint8_t* hops;  uint8_t* raw;  int64_t* counts;      /* err, hops, counts optional */
+    void* scratch;  int64_t scratch_bytes;
+} NsffMotionSpanArgs;
+typedef struct NsffMaskPropagateArgs {
+    int32_t n_frames, H, W, reach;             /* 1 <= reach <= NSFF_PROPAGATE_MAX_REACH */
+    const uint8_t* src;                              /* (F, H*W), 0 dynamic                  */
+    const float* flow_fw;  const float* flow_bw;     /* (F, H*W, 2)                          */
+    const uint8_t* valid;                            /* (F, 2, H*W), optional                */
+    uint8_t* dst;  uint8_t* hits;  int64_t* zero_counts;              /* hits, zero_counts optional */
+    void* scratch;  int64_t scratch_bytes;
+} NsffMaskPropagateArgs;
+int64_t nsff_motion_span_scratch_bytes(int32_t n_frames, int32_t H, int32_t W);
+int     nsff_motion_span(const NsffMotionSpanArgs* args, void* stream);
+int     nsff_mask_propagate(const NsffMaskPropagateArgs* args, void* stream);
+
 /* cdf (n_frames, n) fp64 = per-frame inclusive prefix sum of weights (n_frames, n) fp32 (non-negative). */
 int nsff_cdf(const float* weights, int64_t n_frames, int64_t n, double* cdf, void* stream);
 

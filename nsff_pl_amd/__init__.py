@@ -20,7 +20,7 @@ from .flow import induced_flow, flow_to_image, flow_epe, epe_from_sums
 from . import tracks
 from .tracks import advect, draw
 from . import motion
-from .motion import motion_masks, flow_consistency, fundamental_matrices
+from .motion import motion_masks, flow_consistency, fundamental_matrices, propagate
 from . import optflow
 from .optflow import optical_flow, sequence_flows, refine_flow
 from . import depth
@@ -37,7 +37,7 @@ __all__ = ["NeRF", "PosEmbedding", "render_rays", "sample_pdf", "interpolate", "
            "resize_images", "resize_masks", "resize_disps", "resize_flows", "resize_frames", "scaled_intrinsics",
            "flow", "induced_flow", "flow_to_image", "flow_epe", "epe_from_sums",
            "tracks", "advect", "draw",
-           "motion", "motion_masks", "flow_consistency", "fundamental_matrices",
+           "motion", "motion_masks", "flow_consistency", "fundamental_matrices", "propagate",
            "optflow", "optical_flow", "sequence_flows", "refine_flow",
            "depth", "disparity_maps", "triangulate", "densify", "parallax_matrices", "sequence_geometry",
            "panels", "validation_panels", "error_blend", "LPIPS",

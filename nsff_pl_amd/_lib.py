@@ -291,6 +291,21 @@ class DisparitySpanArgs(C.Structure):
                 ("flow_fw", _fp), ("flow_bw", _fp), ("Pm", _fp), ("valid", _fp), ("masks", _fp), ("n", _fp), ("c", _fp), ("votes", _fp),
                 ("counts", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
 
+MOTION_MAX_SPAN, PROPAGATE_MAX_REACH = 8, 8                                   # NSFF_MOTION_MAX_SPAN, NSFF_PROPAGATE_MAX_REACH
+
+
+class MotionSpanArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("span", C.c_int32),
+                ("threshold", C.c_float), ("pad_", C.c_int32),
+                ("flow_fw", _fp), ("flow_bw", _fp), ("Fm", _fp), ("hop_scale", _fp), ("valid", _fp),
+                ("err", _fp), ("hops", _fp), ("raw", _fp), ("counts", _fp), ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
+
+class MaskPropagateArgs(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reach", C.c_int32),
+                ("src", _fp), ("flow_fw", _fp), ("flow_bw", _fp), ("valid", _fp), ("dst", _fp), ("hits", _fp), ("zero_counts", _fp),
+                ("scratch", _fp), ("scratch_bytes", C.c_int64)]
+
 
 FLOW_MEDIAN_MAX_RADIUS, FLOW_MEDIAN_TILED = 7, 1                              # NSFF_FLOW_MEDIAN_*
 
@@ -461,6 +476,9 @@ _SIGNATURES = {
     "nsff_disparity_dense": (C.c_int, [C.POINTER(DisparityDenseArgs), _fp]),
     "nsff_disparity_span_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "nsff_disparity_span": (C.c_int, [C.POINTER(DisparitySpanArgs), _fp]),
+    "nsff_motion_span_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "nsff_motion_span": (C.c_int, [C.POINTER(MotionSpanArgs), _fp]),
+    "nsff_mask_propagate": (C.c_int, [C.POINTER(MaskPropagateArgs), _fp]),
     "nsff_flow_median": (C.c_int, [C.POINTER(FlowMedianArgs), _fp]),
     "nsff_cdf": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nsff_ray_draw": (C.c_int, [C.POINTER(RayDrawArgs), _fp]),
@@ -1750,6 +1768,72 @@ def disparity_span(flows_fw, flows_bw, Pm, span, valid=None, masks=None, min_par
     with torch.cuda.device(dev):
         _check(load().nsff_disparity_span(C.byref(a), _stream()), "nsff_disparity_span")
     return n, c, votes
+
+
+def motion_span_scratch_bytes(n_frames, H, W):
+    return int(load().nsff_motion_span_scratch_bytes(int(n_frames), int(H), int(W)))
+
+
+def motion_span(flows_fw, flows_bw, Fm, hop_scale, span, valid=None, threshold=1.0, err=None, hops=None, raw=None, counts=None,
+                scratch=None):
+    """nsff_motion_span (csrc/motionspan.hip) on (F, H, W, 2) fp32 flows with the matrices Fm (F, 2, span, 3, 3) fp32 of the neighbours
+    f +- 1 .. f +- span and hop_scale (span) fp32, valid (F, 2, H, W) uint8 optional -> raw (F, H, W) uint8 (0 dynamic, 255 static; a
+    fresh tensor when None), returned; err (F, 2, H, W) fp32, hops (F, 2, H, W) uint8, counts (F, 3) int64 [over fw, over bw, dynamic]
+    -- whichever are given.  scratch: a uint8 tensor of motion_span_scratch_bytes() bytes, zero before its first use (a fresh one
+    when None)."""
+    require_gpu_tensor(flows_fw, "motion_span: flows_fw")
+    F, H, W = (int(v) for v in flows_fw.shape[:3])
+    px, dev, span = F * H * W, flows_fw.device, int(span)
+    if raw is None:
+        raw = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    a = MotionSpanArgs(n_frames=F, H=H, W=W, span=span, threshold=float(threshold))
+    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, px * 2), ("flow_bw", flows_bw, torch.float32, px * 2),
+                                   ("Fm", Fm, torch.float32, F * 18 * span), ("hop_scale", hop_scale, torch.float32, span),
+                                   ("valid", valid, torch.uint8, px * 2), ("err", err, torch.float32, px * 2),
+                                   ("hops", hops, torch.uint8, px * 2), ("raw", raw, torch.uint8, px),
+                                   ("counts", counts, torch.int64, F * 3)):
+        if t is None:
+            continue
+        ptr = _dptr(t, dtype, f"motion_span: {field}")
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"motion_span: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        setattr(a, field, ptr)
+    if counts is not None and scratch is None:
+        scratch = torch.zeros(max(motion_span_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    if scratch is not None:
+        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "motion_span: scratch"), scratch.numel()
+    with torch.cuda.device(dev):
+        _check(load().nsff_motion_span(C.byref(a), _stream()), "nsff_motion_span")
+    return raw
+
+
+def mask_propagate(src, flows_fw, flows_bw, reach, valid=None, dst=None, hits=None, zero_counts=None, scratch=None):
+    """nsff_mask_propagate (csrc/motionspan.hip): dst (F, H, W) uint8 = src with "dynamic" (0) carried along the chained flow from
+    the frames f +- 1 .. f +- reach (a fresh tensor when None), returned; hits (F, H, W) uint8 and zero_counts (F,) int64 where
+    given.  scratch as for motion_span."""
+    require_gpu_tensor(src, "mask_propagate: src")
+    F, H, W = (int(v) for v in src.shape)
+    px, dev = F * H * W, src.device
+    if dst is None:
+        dst = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    a = MaskPropagateArgs(n_frames=F, H=H, W=W, reach=int(reach))
+    for field, t, dtype, numel in (("src", src, torch.uint8, px), ("flow_fw", flows_fw, torch.float32, px * 2),
+                                   ("flow_bw", flows_bw, torch.float32, px * 2), ("valid", valid, torch.uint8, px * 2),
+                                   ("dst", dst, torch.uint8, px), ("hits", hits, torch.uint8, px),
+                                   ("zero_counts", zero_counts, torch.int64, F)):
+        if t is None:
+            continue
+        ptr = _dptr(t, dtype, f"mask_propagate: {field}")
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"mask_propagate: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        setattr(a, field, ptr)
+    if zero_counts is not None and scratch is None:
+        scratch = torch.zeros(max(motion_span_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
+    if scratch is not None:
+        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "mask_propagate: scratch"), scratch.numel()
+    with torch.cuda.device(dev):
+        _check(load().nsff_mask_propagate(C.byref(a), _stream()), "nsff_mask_propagate")
+    return dst
 
 
 def _same_planes(who, first, **others):

@@ -62,6 +62,14 @@ On F = 30 frames also nsff_disparity_span (csrc/parallax.hip) at span 1, 2, 4 an
 nsff_disparity_sparse on the same inputs, all five taken in turn: `span{S}_us` against `span{S}_bound_us`, the (20 S + 9) B per pixel
 it must move at the HBM peak (per direction 10 B for the first vote and 10 B of unique taps per hop; 9 B written), and
 `span{S}_bound_fraction`, the bound over the time; `span1_sparse_us` is the one-frame kernel beside span 1.
+Motion masks over several frames (--only motionspan; csrc/motionspan.hip) at 512 x 288 on F = 1 and F = 30 frames, on the inputs of
+--only disparity: nsff_motion_span at span 1, 2, 4 and 8 with valid, err, hops and counts, nsff_motion_maps and nsff_disparity_span
+(the same spans, the yardstick: the same chain with more arithmetic) on the same inputs, nsff_mask_propagate at reach 1, 2 and 4
+with valid, hits and counts, all taken in turn, the median of 30 (device events); and the whole motion.motion_masks(span=4, reach=2)
+call.  `*_bound_us`: the bytes a call must move at the HBM peak -- the chained test per direction 9 B for the first step (flow,
+valid) and 10 B of unique taps per hop, 11 B written (err, hops, raw): (20 S + 9) B per pixel; the propagation one mask byte per
+step more, src read and dst and hits written: (22 R + 1) B per pixel -- and `*_bound_fraction` the bound over the time.
+--only motionspan_resources needs no GPU: the compiler's report of the two kernels.
 The image-guided weighted median of a flow map (--only flowmedian; csrc/flowmedian.hip) at 512 x 288 on P = 1 and P = 58 pairs, radius 3
 and radius 7, default weights, with `valid`: nsff_flow_median alone on preallocated tensors, the plain and the tiled route taken in
 turn, the median of 30 (device events).  `visits` is what the selection must do whatever the route, 2 components x 32 steps x
@@ -584,15 +592,83 @@ def bench_disparity_span(dev, fw, bw, K, poses, valid, masks, reps, tag):
     return out
 
 
-def disparity_resources():
-    """The compiler's resource report of every kernel of csrc/depth.hip: {kernel: [VGPRs, scratch bytes, LDS bytes, waves per SIMD]}."""
+MOTION_SPANS, MOTION_REACHES = (1, 2, 4, 8), (1, 2, 4)
+
+
+def motion_span_bytes_per_pixel(span):
+    """What nsff_motion_span must move: per direction 9 B for the first step (flow, valid) and 10 B of unique taps per hop; err,
+    hops and raw written (8 + 2 + 1)."""
+    return 20 * span + 9
+
+
+def mask_propagate_bytes_per_pixel(reach):
+    """What nsff_mask_propagate must move: per direction 9 B for the first step, one mask byte per step and 10 B of unique taps per
+    hop; src read, dst and hits written."""
+    return 22 * reach + 1
+
+
+def bench_motionspan(dev, g, W, H, reps, F):
+    """nsff_motion_span, nsff_disparity_span and nsff_mask_propagate at every span / reach, and nsff_motion_maps, on the inputs of
+    bench_disparity, taken in turn; then the whole motion_masks(span=4, reach=2) call."""
+    from nsff_pl_amd import depth, motion
+    px = F * H * W
+    K = np.array([[400.0, 0, W / 2], [0, 400.0, H / 2], [0, 0, 1]])
+    poses = np.tile(np.eye(4)[:3], (F, 1, 1))
+    poses[:, 0, 3] = 0.1 * np.arange(F)
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
+    delta = 0.3 + 0.1 * torch.sin(0.02 * xs + 0.03 * ys)         # a smooth disparity map: the flow is its parallax, 40 delta px, and noise
+    fw = torch.stack([-40.0 * delta, torch.zeros_like(delta)], -1).expand(F, H, W, 2) + 0.05 * torch.randn(F, H, W, 2, device=dev, generator=g)
+    bw = -fw + 0.05 * torch.randn(F, H, W, 2, device=dev, generator=g)
+    valid = (torch.rand(F, 2, H, W, device=dev, generator=g) < 0.9).to(torch.uint8)
+    masks = torch.where((xs - W / 2) ** 2 + (ys - H / 2) ** 2 < (0.2 * H) ** 2, 0, 255).to(torch.uint8).expand(F, H, W).contiguous()
+    scratch = torch.zeros(_lib.motion_maps_scratch_bytes(F, H, W), dtype=torch.uint8, device=dev)
+    err, hops = torch.empty(F, 2, H, W, device=dev), torch.empty(F, 2, H, W, dtype=torch.uint8, device=dev)
+    raw, dst, hits = (torch.empty(F, H, W, dtype=torch.uint8, device=dev) for _ in range(3))
+    counts3, counts5, counts1 = (torch.empty(F, n, dtype=torch.int64, device=dev) for n in (3, 5, 1))
+    sums, valid_out = torch.empty(F, 2, dtype=torch.float64, device=dev), torch.empty(F, 2, H, W, dtype=torch.uint8, device=dev)
+    votes, out2 = torch.empty(F, H, W, dtype=torch.uint8, device=dev), tuple(torch.empty(F, H, W, device=dev) for _ in range(2))
+    Fs = {s: motion.fundamental_matrices(K, poses, span=s).reshape(F, 2, s, 3, 3).contiguous().to(dev) for s in MOTION_SPANS}
+    Ps = {s: depth.parallax_matrices(K, poses, span=s).reshape(F, 2, s, 12).contiguous().to(dev) for s in MOTION_SPANS}
+    scales = {s: torch.from_numpy(motion.default_hop_scale(s)).to(dev) for s in MOTION_SPANS}
+    names, fns = [], []
+    for s in MOTION_SPANS:
+        names.append(f"span{s}")
+        fns.append(lambda s=s: _lib.motion_span(fw, bw, Fs[s], scales[s], s, valid=valid, err=err, hops=hops, raw=raw, counts=counts3, scratch=scratch))
+        names.append(f"disparity_span{s}")
+        fns.append(lambda s=s: _lib.disparity_span(fw, bw, Ps[s], s, valid=valid, masks=masks, counts=counts1, votes=votes, scratch=scratch, out=out2))
+    for r in MOTION_REACHES:
+        names.append(f"propagate{r}")
+        fns.append(lambda r=r: _lib.mask_propagate(masks, fw, bw, r, valid=valid, dst=dst, hits=hits, zero_counts=counts1, scratch=scratch))
+    names.append("motion_maps")
+    fns.append(lambda: _lib.motion_maps(fw, bw, Fs[1].reshape(F, 2, 3, 3), err=err, valid=valid_out, raw=raw, counts=counts5, err_sums=sums, scratch=scratch))
+    times = dict(zip(names, time_alternating_us(fns, reps)))
+    tag = f"motionspan_F{F}"
+    out = {}
+    for s in MOTION_SPANS:
+        fns[names.index(f"span{s}")]()
+        bound = px * motion_span_bytes_per_pixel(s) / HBM_PEAK * 1e6
+        out[f"{tag}_span{s}_us"], out[f"{tag}_span{s}_bound_us"], out[f"{tag}_span{s}_bound_fraction"] = times[f"span{s}"], bound, bound / times[f"span{s}"]
+        out[f"{tag}_span{s}_disparity_span_us"] = times[f"disparity_span{s}"]
+        out[f"{tag}_span{s}_mean_hops"] = float(hops.sum(dtype=torch.int64)) / px
+    out[f"{tag}_motion_maps_us"] = times["motion_maps"]
+    for r in MOTION_REACHES:
+        bound = px * mask_propagate_bytes_per_pixel(r) / HBM_PEAK * 1e6
+        out[f"{tag}_propagate{r}_us"], out[f"{tag}_propagate{r}_bound_us"], out[f"{tag}_propagate{r}_bound_fraction"] = times[f"propagate{r}"], bound, bound / times[f"propagate{r}"]
+    out[f"{tag}_masks_span4_reach2_call_us"] = time_us(lambda: motion.motion_masks(fw, bw, K, poses, span=4, reach=2), reps)
+    out[f"{tag}_masks_default_call_us"] = time_us(lambda: motion.motion_masks(fw, bw, K, poses), reps)
+    return out
+
+
+def disparity_resources(source="depth.hip"):
+    """The compiler's resource report of every kernel of csrc/depth.hip (or of another source of csrc/ built the same way):
+    {kernel: [VGPRs, scratch bytes, LDS bytes, waves per SIMD]}."""
     import re
     import subprocess
     import tempfile
     csrc = os.path.join(ROOT, "nsff_pl_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-               "-Rpass-analysis=kernel-resource-usage", "-c", "depth.hip", "-o", os.path.join(tmp, "depth.o")]
+               "-Rpass-analysis=kernel-resource-usage", "-c", source, "-o", os.path.join(tmp, "out.o")]
         text = subprocess.run(cmd, cwd=csrc, check=True, capture_output=True, text=True).stderr
     out, name = {}, None
     for line in text.splitlines():
@@ -612,10 +688,13 @@ def disparity_resources():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion, optflow, flowmedian, disparity (default: everything but lpips, optflow, flowmedian and disparity); disparity_resources alone needs no GPU")
+    ap.add_argument("--only", default="", help="comma-separated cases to run: finish, flow, panel, resize, lpips, scale, tracks, motion, optflow, flowmedian, disparity, motionspan (default: everything but lpips, optflow, flowmedian, disparity and motionspan); disparity_resources and motionspan_resources alone need no GPU")
     args = ap.parse_args()
     if args.only == "disparity_resources":
         print(json.dumps(disparity_resources()))
+        return
+    if args.only == "motionspan_resources":
+        print(json.dumps(disparity_resources("motionspan.hip")))
         return
     dev = torch.device("cuda:0")
     W, H = 512, 288
@@ -661,6 +740,10 @@ def main():
         if "disparity" in only:
             for F in (1, 30):
                 out.update(bench_disparity(dev, g, W, H, args.reps, F))
+                torch.cuda.empty_cache()
+        if "motionspan" in only:
+            for F in (1, 30):
+                out.update(bench_motionspan(dev, g, W, H, min(args.reps, 30), F))
                 torch.cuda.empty_cache()
         print(json.dumps({k: (round(v, 2) if v >= 0.01 else float(f"{v:.3g}")) if isinstance(v, float) else v for k, v in out.items()}))
         return
