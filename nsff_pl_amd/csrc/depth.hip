@@ -8,8 +8,9 @@
 // no data-dependent loop; the frame is a grid dimension of every kernel and a call is a fixed list of launches.
 //
 // disparity_sparse_kernel -- all F frames and both directions in one launch, on the pixel quads of nsff_frame_ops.h: the
-//   least-squares disparity of a pixel over its voting directions as the pair (n, c), c the parallax in px^2 and n = c * disparity,
-//   and the per-frame count of known pixels through the ticketed reduction of nsff_frame_ops.h.
+//   least-squares disparity of a pixel over its voting directions as the pair (n, c), c the parallax in px^2 and n = c * disparity
+//   (the vote is parallax_vote of nsff_flow_chain.h, which nsff_disparity_span of parallax.hip takes along a chain of flows), and
+//   the per-frame count of known pixels through frame_count_finish of nsff_frame_ops.h.
 // push_kernel / pull_kernel -- one step up and one step down the 2 x 2 pyramid that runs to 1 x 1: sums of clipped blocks in
 //   row-major order on the way up, n / c or the parent's value on the way down (without c / n: the parent's value alone, the
 //   nearest-neighbour upsampling).
@@ -25,39 +26,25 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
-#include <cfloat>
 
 #include "../../include/nsff_render.h"
 #include "nsff_common.h"
-#include "nsff_frame_ops.h"
+#include "nsff_flow_chain.h"
 
 namespace {
 
-constexpr float FLOW_THRESH = 1e7f;                               // flowlib's UNKNOWN_FLOW_THRESH
 constexpr int DP_THREADS = 256;
 constexpr int DP_BX = 64, DP_BY = 4;                              // a workgroup of the per-pixel kernels: 64 x 4 pixels
-
-// both components within the threshold; a NaN fails the comparison
-__device__ __forceinline__ bool flow_known(float u, float v) { return fabsf(u) <= FLOW_THRESH && fabsf(v) <= FLOW_THRESH; }
 
 // ---- sparse ----
 __global__ __launch_bounds__(FIN_THREADS) void disparity_sparse_kernel(NsffDisparitySparseArgs a, float mp2, int aligned,
                                                                        unsigned* __restrict__ counters, frame_word* __restrict__ partials) {
-    __shared__ uint32_t s_cnt[FIN_THREADS / 64][1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t f = blockIdx.y, HW = (int64_t)a.H * a.W;
     const Quad q = quad_of(blockIdx.x, tid, f, HW, aligned);
 
-    int pxs[FIN_PX], pys[FIN_PX];                                 // the lane's four pixels, as motion_map_kernel steps them
-    {
-        const int p = (int)min(q.p0, HW - 1);
-        int py = p / a.W, px = p - py * a.W;
-#pragma unroll
-        for (int i = 0; i < FIN_PX; ++i) {
-            pxs[i] = px; pys[i] = py;
-            if (++px == a.W) { px = 0; ++py; }
-        }
-    }
+    float xs[FIN_PX], ys[FIN_PX];
+    quad_pixels(q, HW, a.W, xs, ys);
     float num[FIN_PX] = {0.f, 0.f, 0.f, 0.f}, den[FIN_PX] = {0.f, 0.f, 0.f, 0.f}, par[FIN_PX] = {0.f, 0.f, 0.f, 0.f};
     bool is_static[FIN_PX];
 #pragma unroll
@@ -74,17 +61,8 @@ __global__ __launch_bounds__(FIN_THREADS) void disparity_sparse_kernel(NsffDispa
 #pragma unroll
         for (int i = 0; i < FIN_PX; ++i) {
             const float u = av[2 * i], v = av[2 * i + 1];
-            const float x = (float)pxs[i], y = (float)pys[i];
-            const float hx = (P[0] * x + P[1] * y) + P[2];
-            const float hy = (P[3] * x + P[4] * y) + P[5];
-            const float hz = (P[6] * x + P[7] * y) + P[8];
-            const float up = x + u, vp = y + v;
-            const float r = 1.f / hz;
-            const float ax = (P[9] - up * P[11]) * r, ay = (P[10] - vp * P[11]) * r;
-            const float bx = up - hx * r, by = vp - hy * r;
-            const float p2 = bx * bx + by * by;
-            const float ab = ax * bx + ay * by;
-            const float aa = ax * ax + ay * ay;
+            float p2, ab, aa, hz;
+            parallax_vote(P, xs[i], ys[i], xs[i] + u, ys[i] + v, p2, ab, aa, hz);
             bool vote = row && i < q.n && flow_known(u, v) && is_static[i] && hz > 0.f && p2 >= mp2;
             if (a.valid) vote = vote && i < q.n && a.valid[plane + i] != 0;
             num[i] = num[i] + (vote ? ab : 0.f);
@@ -105,24 +83,7 @@ __global__ __launch_bounds__(FIN_THREADS) void disparity_sparse_kernel(NsffDispa
         store_px<1>(a.c, q, cv);
         store_px<1>(a.n, q, nv);
     }
-    if (!a.counts) return;
-
-    cnt = wave_sum(cnt);
-    if (lane == 0) s_cnt[wave][0] = cnt;
-    __syncthreads();
-    if (wave != 0) return;
-    const unsigned n_blocks = gridDim.x;
-    frame_word* fp = partials + f * n_blocks;
-    const frame_word mine[1] = {pack2(sum4(s_cnt, 0), 0u)};
-    if (!frame_publish(fp, counters + f, blockIdx.x, n_blocks, lane, mine)) return;
-    long long total = 0;
-    frame_fold<1>(fp, n_blocks, lane, [&](const frame_word (&w)[1]) { total += (long long)word_lo(w[0]); });
-    for (unsigned b = lane; b < n_blocks; b += 64) fp[b] = 0ull;  // the scratch is all zero again
-    total = wave_sum(total);
-    if (lane == 0) {
-        a.counts[f] = (int64_t)total;
-        frame_counter_reset(counters + f);
-    }
+    if (a.counts) frame_count_finish<1, FIN_THREADS>({cnt}, a.counts, counters, partials, f);
 }
 
 // ---- the pyramid ----
@@ -267,9 +228,6 @@ inline bool planes_ok(int32_t n, int32_t H, int32_t W) {
     return frame_dims_ok(n, H, W) && H <= 65535 * DP_BY && (int64_t)n * H * W <= 0x7fffffffLL;
 }
 inline dim3 pixel_grid(int32_t n, int32_t H, int32_t W) { return dim3((W + DP_BX - 1) / DP_BX, (H + DP_BY - 1) / DP_BY, n); }
-inline bool off4(const void* p) { return ((uintptr_t)p & 3) != 0; }
-inline bool positive(float v) { return v > 0.f && v <= 3.0e38f; }
-inline bool not_negative(float v) { return v >= 0.f && v <= 3.0e38f; }
 
 inline int fused_pair_ok(int tile, int k) {
     return (tile == 32 && (k == 2 || k == 3 || k == 4 || k == 6)) || (tile == 16 && k == 2);
@@ -308,7 +266,7 @@ inline int relax_launches(int iters, int fused, int k) { return fused ? (iters +
 // the route's checks, shared by nsff_disparity_relax and nsff_disparity_dense; tile / k come back resolved
 int check_route(int32_t iters, int32_t fused, int32_t& tile, int32_t& k, float lambda, float sigma) {
     if (iters < 0 || iters > 100000 || (fused != 0 && fused != 1)) return NSFF_ERR_INVALID;
-    if (!not_negative(lambda) || !positive(sigma)) return NSFF_ERR_INVALID;
+    if (!bounded_not_negative(lambda) || !bounded_positive(sigma)) return NSFF_ERR_INVALID;
     if (tile == 0 && k == 0) { tile = NSFF_DISPARITY_TILE; k = NSFF_DISPARITY_K; }
     if (fused && !fused_pair_ok(tile, k)) return NSFF_ERR_INVALID;
     return NSFF_OK;
@@ -350,7 +308,7 @@ extern "C" int64_t nsff_disparity_sparse_scratch_bytes(int32_t n_frames, int32_t
 extern "C" int nsff_disparity_sparse(const NsffDisparitySparseArgs* a, void* stream) {
     if (!a) return NSFF_ERR_NULL;
     if (!frame_dims_ok(a->n_frames, a->H, a->W)) return NSFF_ERR_INVALID;
-    if (!not_negative(a->min_parallax)) return NSFF_ERR_INVALID;
+    if (!bounded_not_negative(a->min_parallax)) return NSFF_ERR_INVALID;
     if (!a->flow_fw || !a->flow_bw || !a->Pm || !a->n || !a->c) return NSFF_ERR_NULL;
     if (a->counts && !a->scratch) return NSFF_ERR_NULL;
     if (a->counts && a->scratch_bytes < nsff_disparity_sparse_scratch_bytes(a->n_frames, a->H, a->W)) return NSFF_ERR_INVALID;

@@ -31,17 +31,13 @@
 
 #include "../../include/nsff_render.h"
 #include "nsff_common.h"
-#include "nsff_frame_ops.h"
+#include "nsff_flow_chain.h"
 
 namespace {
 
 constexpr int FLOW_THREADS = 256, FLOW_PX = 4, FLOW_BLOCK_PX = FLOW_THREADS * FLOW_PX;
 constexpr int FLOW_WORDS = 11;                                    // one workgroup's share of a frame: 6 fp64 sums, 6 uint32 counts, 4 fp32 radii
-constexpr float FLOW_THRESH = 1e7f;                               // flowlib's UNKNOWN_FLOW_THRESH
 constexpr int WHEEL = 55;                                         // RY 15 + YG 6 + GC 4 + CB 11 + BM 13 + MR 6
-
-// both components within the threshold; a NaN fails the comparison
-__device__ __forceinline__ bool flow_known(float u, float v) { return fabsf(u) <= FLOW_THRESH && fabsf(v) <= FLOW_THRESH; }
 
 __global__ __launch_bounds__(FLOW_THREADS) void flow_map_kernel(NsffFlowMapsArgs a, int reduce, unsigned* __restrict__ counters,
                                                                 frame_word* __restrict__ partials) {

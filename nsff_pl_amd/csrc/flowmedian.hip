@@ -24,10 +24,10 @@
 
 #include "../../include/nsff_render.h"
 #include "nsff_common.h"
+#include "nsff_flow_chain.h"
 
 namespace {
 
-constexpr float FLOW_THRESH = 1e7f;                               // flowlib's UNKNOWN_FLOW_THRESH
 constexpr int MAX_R = NSFF_FLOW_MEDIAN_MAX_RADIUS;
 constexpr int MAX_SIDE = 2 * MAX_R + 1;
 constexpr int TILE_W = 32, TILE_H = 8, THREADS = TILE_W * TILE_H;
@@ -39,9 +39,6 @@ struct MedianParams {
     const float2* flow;  const float* grey;  const uint8_t* valid;  float2* out;
     float s[MAX_SIDE * MAX_SIDE];                                 // 1 + (dx^2 + dy^2) / sigma_s^2, rows of 2 r + 1
 };
-
-// both components within the threshold; a NaN fails the comparison
-__device__ __forceinline__ bool flow_known(float2 w) { return fabsf(w.x) <= FLOW_THRESH && fabsf(w.y) <= FLOW_THRESH; }
 
 __device__ __forceinline__ uint32_t key_of(float v) {
     uint32_t b = __float_as_uint(v);
@@ -187,8 +184,6 @@ void launch_tiled(const MedianParams& p, int32_t n_pairs, hipStream_t st) {
     hipLaunchKernelGGL(flow_median_tiled<R>, grid, dim3(THREADS), 0, st, p);
 }
 
-inline bool positive(float v) { return v > 0.f && v <= 3.0e38f; }
-
 }  // namespace
 
 extern "C" int nsff_flow_median(const NsffFlowMedianArgs* a, void* stream) {
@@ -196,14 +191,12 @@ extern "C" int nsff_flow_median(const NsffFlowMedianArgs* a, void* stream) {
     if (a->n_pairs < 1 || a->n_pairs > 65535 || a->H < 1 || a->W < 1 || a->H > 32768 || a->W > 32768) return NSFF_ERR_INVALID;
     if ((int64_t)a->n_pairs * a->H * a->W >= ((int64_t)1 << 31)) return NSFF_ERR_INVALID;
     if (a->radius < 1 || a->radius > MAX_R || (a->tiled != 0 && a->tiled != 1)) return NSFF_ERR_INVALID;
-    if (!positive(a->sigma_i) || !positive(a->sigma_s)) return NSFF_ERR_INVALID;
+    if (!bounded_positive(a->sigma_i) || !bounded_positive(a->sigma_s)) return NSFF_ERR_INVALID;
     if (!a->flow || !a->grey || !a->out) return NSFF_ERR_NULL;
     if (((uintptr_t)a->flow | (uintptr_t)a->out) & 7) return NSFF_ERR_ALIGN;
     if ((uintptr_t)a->grey & 3) return NSFF_ERR_ALIGN;
-    {                                                             // out must not overlap flow: a pixel's neighbours are read after it is written
-        const uintptr_t f = (uintptr_t)a->flow, o = (uintptr_t)a->out, bytes = (uintptr_t)a->n_pairs * a->H * a->W * 8u;
-        if (o < f + bytes && f < o + bytes) return NSFF_ERR_INVALID;
-    }
+    // out must not overlap flow: a pixel's neighbours are read after it is written
+    if (overlap(a->flow, a->out, (int64_t)a->n_pairs * a->H * a->W * 8)) return NSFF_ERR_INVALID;
 
     MedianParams p = {};
     p.H = a->H; p.W = a->W; p.r = a->radius; p.sigma_i = a->sigma_i;

@@ -14,7 +14,8 @@
 //     s = a + b, lhs = s.u s.u + s.v s.v, rhs = alpha ((a.u a.u + a.v a.v) + (b.u b.u + b.v b.v)) + beta, consistent: lhs <= rhs
 //     l_i = (M[i][0] x + M[i][1] y) + M[i][2], r = (l0 qx + l1 qy) + l2, n = l0 l0 + l1 l1, e = |r| / sqrtf(n), line_ok: 0 < n < inf
 //   err = e where neighbour, known and line_ok, else NSFF_FLOW_UNKNOWN; valid = neighbour, known, inside, taps, consistent, line_ok;
-//   raw = 0 where a direction is valid with e > threshold, else 255.  The taps are read without a branch, from q clamped into the
+//   raw = 0 where a direction is valid with e > threshold, else 255.  flow_known, bilerp and line_distance are nsff_flow_chain.h's,
+//   which nsff_motion_span (motionspan.hip) measures with too.  The taps are read without a branch, from q clamped into the
 //   image (the identity where q is inside, where alone they are used), so no address leaves the neighbour's frame whatever the
 //   flow holds and the sixteen loads of a lane's four pixels are in flight together.
 //
@@ -22,38 +23,25 @@
 // and valid are (F, 2, H*W), so a direction's plane f * 2 + d has a quad of its own (its flat index decides whether it is
 // vectorised).  Per frame: the counts of valid and over pixels and the fp64 sum of e over the valid ones, per direction, and the
 // count of dynamic pixels -- the ticketed reduction of nsff_frame_ops.h; the frame's last workgroup also returns the partials it
-// read to zero, so the scratch is all zero between calls.
+// read to zero, so the scratch is all zero between calls.  (The tail carries fp64 sums beside its counts, so it is written out
+// here; a kernel that only counts ends in frame_count_finish.)
 //
 // nsff_mask_erode, one launch:
 //
 // mask_erode_kernel -- the minimum over a k x k window, separable: a 64 x 32 tile with its halo of k / 2 pixels goes to LDS (as
 //   ssim_kernel holds its tile), pixels outside the image as 255 -- they do not contribute, OpenCV's default border for morphology --
-//   then a horizontal and a vertical pass of k minima each.  The count of zero pixels per frame goes the same ticketed way.
+//   then a horizontal and a vertical pass of k minima each.  The count of zero pixels per frame goes through frame_count_finish.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
-#include <cfloat>
 
 #include "../../include/nsff_render.h"
 #include "nsff_common.h"
-#include "nsff_frame_ops.h"
+#include "nsff_flow_chain.h"
 
 namespace {
 
 constexpr int MOTION_WORDS = 5;                                   // one workgroup's share of a frame: 2 fp64 sums, 5 uint32 counts
-constexpr float FLOW_THRESH = 1e7f;                               // flowlib's UNKNOWN_FLOW_THRESH
-
-// both components within the threshold; a NaN fails the comparison
-__device__ __forceinline__ bool flow_known(float u, float v) { return fabsf(u) <= FLOW_THRESH && fabsf(v) <= FLOW_THRESH; }
-__device__ __forceinline__ bool flow_known(float2 w) { return flow_known(w.x, w.y); }
-
-// B at (qx, qy) inside the image, one component: ((B00 (1 - ax) + B01 ax) (1 - ay)) + ((B10 (1 - ax) + B11 ax) ay)
-__device__ __forceinline__ float bilerp(float b00, float b01, float b10, float b11, float ax, float omx, float ay, float omy) {
-    const float top = b00 * omx + b01 * ax;
-    const float bot = b10 * omx + b11 * ax;
-    return (top * omy) + (bot * ay);
-}
-
 __global__ __launch_bounds__(FIN_THREADS) void motion_map_kernel(NsffMotionMapsArgs a, int aligned, unsigned* __restrict__ counters,
                                                                  frame_word* __restrict__ partials) {
     __shared__ double s_sum[FIN_THREADS / 64][2];
@@ -63,17 +51,10 @@ __global__ __launch_bounds__(FIN_THREADS) void motion_map_kernel(NsffMotionMapsA
     const Quad q = quad_of(blockIdx.x, tid, f, HW, aligned);
     const float wmax = (float)(a.W - 1), hmax = (float)(a.H - 1);
 
-    // the lane's four pixels: (x, y) of the first by one division, the others by stepping (any W >= 1)
+    // The lane's four pixels (pxs, pys), held as ints and converted at each use: held as floats the kernel takes 94 VGPRs for 100 and runs five waves a SIMD for four, and
+    // measured 3.8 % slower at 512 x 288, F = 30 on random flow.
     int pxs[FIN_PX], pys[FIN_PX];
-    {
-        const int p = (int)min(q.p0, HW - 1);
-        int py = p / a.W, px = p - py * a.W;
-#pragma unroll
-        for (int i = 0; i < FIN_PX; ++i) {
-            pxs[i] = px; pys[i] = py;
-            if (++px == a.W) { px = 0; ++py; }
-        }
-    }
+    quad_pixels(q, HW, a.W, pxs, pys);
 
     double sum[2] = {0.0, 0.0};
     uint32_t cnt[5] = {0u, 0u, 0u, 0u, 0u};                       // valid fw, valid bw, over fw, over bw, dynamic
@@ -121,13 +102,9 @@ __global__ __launch_bounds__(FIN_THREADS) void motion_map_kernel(NsffMotionMapsA
                 bool ok = kn && inside && flow_known(b00[i]) && flow_known(b01[i]) && flow_known(b10[i]) && flow_known(b11[i]) && lhs <= rhs;
                 bool over = false;
                 if (a.epipolar) {                                 // (uniform)
-                    const float l0 = (M[0] * x + M[1] * y) + M[2];
-                    const float l1 = (M[3] * x + M[4] * y) + M[5];
-                    const float l2 = (M[6] * x + M[7] * y) + M[8];
-                    const float r = (l0 * qx + l1 * qy) + l2;
-                    const float nn = l0 * l0 + l1 * l1;
-                    const float e = fabsf(r) / sqrtf(nn);
-                    const bool line_ok = nn > 0.f && nn <= FLT_MAX;   // finite and positive; a NaN fails both
+                    float e;
+                    bool line_ok;
+                    line_distance(M, x, y, qx, qy, e, line_ok);
                     if (kn && line_ok) ev[i] = e;
                     ok = ok && line_ok;
                     over = ok && e > a.threshold;
@@ -205,7 +182,6 @@ __global__ __launch_bounds__(ER_THREADS) void mask_erode_kernel(NsffMaskErodeArg
                                                                 frame_word* __restrict__ partials) {
     __shared__ uint8_t s_in[ER_PH][ER_PW];
     __shared__ uint8_t s_h[ER_PH][ER_TW];
-    __shared__ uint32_t s_cnt[ER_THREADS / 64][1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
     const int x0 = tile_x * ER_TW, y0 = tile_y * ER_TH;
@@ -250,31 +226,12 @@ __global__ __launch_bounds__(ER_THREADS) void mask_erode_kernel(NsffMaskErodeArg
             zeros += m == 0u ? 1u : 0u;
         }
     }
-    if (!a.zero_counts) return;
-
-    zeros = wave_sum(zeros);
-    if (lane == 0) s_cnt[wave][0] = zeros;
-    __syncthreads();
-    if (wave != 0) return;
-    const unsigned n_tiles = gridDim.x;
-    frame_word* fp = partials + f * n_tiles;
-    const frame_word mine[1] = {pack2(sum4(s_cnt, 0), 0u)};
-    if (!frame_publish(fp, counters + f, blockIdx.x, n_tiles, lane, mine)) return;
-    long long n = 0;
-    frame_fold<1>(fp, n_tiles, lane, [&](const frame_word (&w)[1]) { n += (long long)word_lo(w[0]); });
-    for (unsigned b = lane; b < n_tiles; b += 64) fp[b] = 0ull;   // the scratch is all zero again
-    n = wave_sum(n);
-    if (lane == 0) {
-        a.zero_counts[f] = (int64_t)n;
-        frame_counter_reset(counters + f);
-    }
+    if (a.zero_counts) frame_count_finish<1, ER_THREADS>({zeros}, a.zero_counts, counters, partials, f);
 }
 
 inline int64_t erode_tiles(int32_t H, int32_t W) {
     return (((int64_t)W + ER_TW - 1) / ER_TW) * (((int64_t)H + ER_TH - 1) / ER_TH);
 }
-// a value that is neither negative nor NaN
-inline bool not_negative(float v) { return v >= 0.f; }
 
 }  // namespace
 
@@ -299,7 +256,7 @@ extern "C" int nsff_motion_maps(const NsffMotionMapsArgs* a, void* stream) {
     if (a->counts && a->scratch_bytes < frame_scratch_bytes(a->n_frames, fin_blocks((int64_t)a->H * a->W), MOTION_WORDS)) return NSFF_ERR_INVALID;
     if ((uintptr_t)a->scratch & 15) return NSFF_ERR_ALIGN;
     if (((uintptr_t)a->flow_fw | (uintptr_t)a->flow_bw | (uintptr_t)a->counts | (uintptr_t)a->err_sums) & 7) return NSFF_ERR_ALIGN;
-    if (((uintptr_t)a->Fm | (uintptr_t)a->err) & 3) return NSFF_ERR_ALIGN;
+    if (off4(a->Fm) || off4(a->err)) return NSFF_ERR_ALIGN;
     const int aligned = ((((uintptr_t)a->flow_fw | (uintptr_t)a->flow_bw | (uintptr_t)a->err) & 15) == 0
                          && (((uintptr_t)a->valid | (uintptr_t)a->raw) & 3) == 0) ? 1 : 0;
     const FrameScratch s = frame_scratch_split(a->counts ? a->scratch : nullptr, a->n_frames);

@@ -83,7 +83,66 @@ __device__ __forceinline__ void frame_fold(const frame_word* frame_partials, uns
 // by one lane, after the frame's outputs: ready for the next launch
 __device__ __forceinline__ void frame_counter_reset(unsigned* counter) { __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// ---- (c) host side: frame limits and the scratch layout ----
+// The whole tail of a kernel that counts N uint32 values per frame, called by every thread of a workgroup of frame f -- of THREADS
+// threads, the constant of the kernel's __launch_bounds__ and of its launch, which must be the four waves that sum4 adds --
+// (grid.x the frame's workgroups, which hold (N + 1) / 2 words each in `partials`): cnt summed over the workgroup, two counts to a
+// word ({c0, c1}, {c2, 0}), published; the frame's last workgroup folds them in block order into out[f * N ..] as int64, returns the
+// partials it read to zero -- the scratch is all zero between calls -- and resets the frame's counter.
+template <int N, int THREADS>
+__device__ __forceinline__ void frame_count_finish(const uint32_t (&cnt)[N], int64_t* __restrict__ out, unsigned* __restrict__ counters,
+                                                   frame_word* __restrict__ partials, int64_t f) {
+    static_assert(THREADS == 4 * 64, "frame_count_finish adds the counts of four waves (sum4)");
+    constexpr int WORDS = (N + 1) / 2;
+    __shared__ uint32_t s_cnt[THREADS / 64][N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t c[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) c[k] = wave_sum(cnt[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s_cnt[wave][k] = c[k];
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    const unsigned n_blocks = gridDim.x;
+    frame_word* fp = partials + f * n_blocks * WORDS;
+    uint32_t tot[2 * WORDS] = {};
+#pragma unroll
+    for (int k = 0; k < N; ++k) tot[k] = sum4(s_cnt, k);
+    frame_word mine[WORDS];
+#pragma unroll
+    for (int i = 0; i < WORDS; ++i) mine[i] = pack2(tot[2 * i], tot[2 * i + 1]);
+    if (!frame_publish(fp, counters + f, blockIdx.x, n_blocks, lane, mine)) return;
+    long long n[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) n[k] = 0;
+    frame_fold<WORDS>(fp, n_blocks, lane, [&](const frame_word (&w)[WORDS]) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) n[k] += (long long)((k & 1) ? word_hi(w[k / 2]) : word_lo(w[k / 2]));
+    });
+    for (unsigned b = lane; b < n_blocks; b += 64)                // what this lane read goes back to zero
+#pragma unroll
+        for (int i = 0; i < WORDS; ++i) fp[(int64_t)b * WORDS + i] = 0ull;
+#pragma unroll
+    for (int k = 0; k < N; ++k) n[k] = wave_sum(n[k]);
+    if (lane == 0) {
+        for (int k = 0; k < N; ++k) out[f * N + k] = (int64_t)n[k];
+        frame_counter_reset(counters + f);
+    }
+}
+
+// ---- (c) host side: argument checks, frame limits and the scratch layout ----
+inline bool off4(const void* p) { return ((uintptr_t)p & 3) != 0; }
+// n bytes from a and n bytes from b share a byte
+inline bool overlap(const void* a, const void* b, int64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)n && y < x + (uintptr_t)n;
+}
+// neither negative nor NaN; +inf passes (a threshold nothing exceeds)
+inline bool not_negative(float v) { return v >= 0.f; }
+// a parameter that is squared or divided by: no NaN, and small enough to stay finite
+inline bool bounded_not_negative(float v) { return v >= 0.f && v <= 3.0e38f; }
+inline bool bounded_positive(float v) { return v > 0.f && v <= 3.0e38f; }
 inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 // grid.y = frame; pixel indices within a frame are ints
 inline bool frame_dims_ok(int32_t n_frames, int32_t H, int32_t W) {

@@ -4,9 +4,19 @@
 // the parallax while the chained flow's noise grows like sqrt(k).
 //
 // include/nsff_render.h states every step as a chain of single fp32 operations; this file is built -ffp-contract=off and
-// tests/parallax_numpy.py is the same chain in numpy, compared bit for bit.  The vote's arithmetic is depth.hip's
-// disparity_sparse_kernel restated (depth.hip itself stays as it is): with span = 1 the two kernels give the same bits, which
-// tests/test_parallax_gpu.py pins.
+// tests/parallax_numpy.py is the same chain in numpy, compared bit for bit.  The vote is parallax_vote of nsff_flow_chain.h, which
+// depth.hip's disparity_sparse_kernel calls too: with span = 1 the two kernels give the same bits, which
+// tests/test_parallax_gpu.py pins.  flow_known, bilerp, the paired tap loads, quad_pixels and the count's tail are shared as well.
+//
+// The hop itself is written out here and NOT taken from nsff_flow_chain.h's Chain / hop_taps / hop_pixel, which motionspan.hip
+// calls: it is the same hop with a second byte plane (`masks`), but built on those helpers this kernel compiles to 121 VGPRs for 111
+// and moves 144 scalar registers through vector lanes in the hop loop for 96, and measured 2.2 to 3.0 % slower at span 4 and 8
+// (512 x 288, F = 30, taken in turn with the parent's build in two calls: span 4 145.4, 145.6 against 141.2, 142.0 us, span 8 252.0,
+// 252.2 against 246.0, 247.2).  The margin is the larger of the two parent runs' difference in the call and 2 %, so this is just
+// outside it, in both calls: a marginal result, worth taking again when the compiler changes.  With four waves a SIMD asked for
+// (110 VGPRs) the compiler waits after every byte load and the kernel is 16 to 32 % slower; three other spellings of the chain
+// state measured as the first.  Until then a fix to the tap addressing is made in hop_taps AND here; tests/test_parallax_gpu.py and tests/test_motionspan_gpu.py pin both to their twins,
+// which share one numpy hop.
 //
 // disparity_span_kernel -- all F frames, both directions and all hops in ONE launch, on the pixel quads of nsff_frame_ops.h.  Frame
 //   f, direction d (0: s = +1, flow_fw; 1: s = -1, flow_bw): the chain starts with A = flow_d[f] at the pixel; at step k it VOTES with
@@ -21,59 +31,26 @@
 //   xl = min(x0, W - 2) on, so that at the right edge, where x1 == x0 == W - 1, the pair still lies in the row: a hop costs a lane
 //   24 gathers instead of 48, and measured 27 us instead of 47 at 512 x 288, F = 30.  A frame one pixel
 //   wide has no such pair and reads its single column.
-//   The known pixels of each frame are counted through the ticketed reduction of nsff_frame_ops.h.
+//   The known pixels of each frame are counted through frame_count_finish of nsff_frame_ops.h.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
-#include <cfloat>
 
 #include "../../include/nsff_render.h"
 #include "nsff_common.h"
-#include "nsff_frame_ops.h"
+#include "nsff_flow_chain.h"
 
 namespace {
 
-constexpr float FLOW_THRESH = 1e7f;                               // flowlib's UNKNOWN_FLOW_THRESH
-
-// both components within the threshold; a NaN fails the comparison
-__device__ __forceinline__ bool flow_known(float u, float v) { return fabsf(u) <= FLOW_THRESH && fabsf(v) <= FLOW_THRESH; }
-__device__ __forceinline__ bool flow_known(float2 w) { return flow_known(w.x, w.y); }
-
-// B at (qx, qy) inside the image, one component: ((B00 (1 - ax) + B01 ax) (1 - ay)) + ((B10 (1 - ax) + B11 ax) ay)
-__device__ __forceinline__ float bilerp(float b00, float b01, float b10, float b11, float ax, float omx, float ay, float omy) {
-    const float top = b00 * omx + b01 * ax;
-    const float bot = b10 * omx + b11 * ax;
-    return (top * omy) + (bot * ay);
-}
-
-// Two horizontally adjacent taps in one load -- a hop is bound by the number of gathers a lane issues, not by their bytes: 16 bytes
-// of flow at an 8-byte aligned address, two bytes of valid / masks at any address.
-typedef float flow_pair __attribute__((ext_vector_type(4), aligned(8)));
-typedef uint16_t byte_pair __attribute__((aligned(1)));
-// the bytes at p[0] (only where `first`) and p[1] are both non-zero
-__device__ __forceinline__ bool pair_set(const uint8_t* p, bool first) {
-    const uint32_t v = *reinterpret_cast<const byte_pair*>(p);
-    return ((v >> 8) != 0u) & (!first | ((v & 0xffu) != 0u));
-}
-
 __global__ __launch_bounds__(FIN_THREADS) void disparity_span_kernel(NsffDisparitySpanArgs a, float mp2, int aligned,
                                                                      unsigned* __restrict__ counters, frame_word* __restrict__ partials) {
-    __shared__ uint32_t s_cnt[FIN_THREADS / 64][1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t f = blockIdx.y, HW = (int64_t)a.H * a.W;
     const Quad q = quad_of(blockIdx.x, tid, f, HW, aligned);
     const float wmax = (float)(a.W - 1), hmax = (float)(a.H - 1);
 
-    float xs[FIN_PX], ys[FIN_PX];                                 // the lane's four pixels, as disparity_sparse_kernel steps them
-    {
-        const int p = (int)min(q.p0, HW - 1);
-        int py = p / a.W, px = p - py * a.W;
-#pragma unroll
-        for (int i = 0; i < FIN_PX; ++i) {
-            xs[i] = (float)px; ys[i] = (float)py;
-            if (++px == a.W) { px = 0; ++py; }
-        }
-    }
+    float xs[FIN_PX], ys[FIN_PX];
+    quad_pixels(q, HW, a.W, xs, ys);
     float num[FIN_PX] = {0.f, 0.f, 0.f, 0.f}, den[FIN_PX] = {0.f, 0.f, 0.f, 0.f}, par[FIN_PX] = {0.f, 0.f, 0.f, 0.f};
     uint32_t nv[FIN_PX] = {0u, 0u, 0u, 0u};
     bool is_static[FIN_PX];
@@ -153,19 +130,10 @@ __global__ __launch_bounds__(FIN_THREADS) void disparity_span_kernel(NsffDispari
             for (int i = 0; i < 12; ++i) { P[i] = a.Pm[((f * 2 + d) * a.span + (k - 1)) * 12 + i]; row = row || P[i] != 0.f; }
 #pragma unroll
             for (int i = 0; i < FIN_PX; ++i) {
-                // ---- the vote: the arithmetic of disparity_sparse_kernel (depth.hip), restated ----
                 const float u = A[2 * i], v = A[2 * i + 1];
-                const float x = xs[i], y = ys[i];
-                const float hx = (P[0] * x + P[1] * y) + P[2];
-                const float hy = (P[3] * x + P[4] * y) + P[5];
-                const float hz = (P[6] * x + P[7] * y) + P[8];
-                const float up = x + u, vp = y + v;
-                const float r = 1.f / hz;
-                const float ax = (P[9] - up * P[11]) * r, ay = (P[10] - vp * P[11]) * r;
-                const float bx = up - hx * r, by = vp - hy * r;
-                const float p2 = bx * bx + by * by;
-                const float ab = ax * bx + ay * by;
-                const float aa = ax * ax + ay * ay;
+                const float up = xs[i] + u, vp = ys[i] + v;
+                float p2, ab, aa, hz;
+                parallax_vote(P, xs[i], ys[i], up, vp, p2, ab, aa, hz);
                 const bool vote = alive[i] && row && hz > 0.f && p2 >= mp2;
                 num[i] = num[i] + (vote ? ab : 0.f);
                 den[i] = den[i] + (vote ? aa : 0.f);
@@ -200,28 +168,8 @@ __global__ __launch_bounds__(FIN_THREADS) void disparity_span_kernel(NsffDispari
         store_px<1>(a.n, q, nn);
         if (a.votes) store_bytes<FIN_PX>(a.votes + q.q0, nv, q.n, q.vec);
     }
-    if (!a.counts) return;
-
-    cnt = wave_sum(cnt);
-    if (lane == 0) s_cnt[wave][0] = cnt;
-    __syncthreads();
-    if (wave != 0) return;
-    const unsigned n_blocks = gridDim.x;
-    frame_word* fp = partials + f * n_blocks;
-    const frame_word mine[1] = {pack2(sum4(s_cnt, 0), 0u)};
-    if (!frame_publish(fp, counters + f, blockIdx.x, n_blocks, lane, mine)) return;
-    long long total = 0;
-    frame_fold<1>(fp, n_blocks, lane, [&](const frame_word (&w)[1]) { total += (long long)word_lo(w[0]); });
-    for (unsigned b = lane; b < n_blocks; b += 64) fp[b] = 0ull;  // the scratch is all zero again
-    total = wave_sum(total);
-    if (lane == 0) {
-        a.counts[f] = (int64_t)total;
-        frame_counter_reset(counters + f);
-    }
+    if (a.counts) frame_count_finish<1, FIN_THREADS>({cnt}, a.counts, counters, partials, f);
 }
-
-inline bool off4(const void* p) { return ((uintptr_t)p & 3) != 0; }
-inline bool not_negative(float v) { return v >= 0.f && v <= 3.0e38f; }
 
 }  // namespace
 
@@ -234,7 +182,7 @@ extern "C" int nsff_disparity_span(const NsffDisparitySpanArgs* a, void* stream)
     if (!a) return NSFF_ERR_NULL;
     if (!frame_dims_ok(a->n_frames, a->H, a->W)) return NSFF_ERR_INVALID;
     if (a->span < 1 || a->span > NSFF_DISPARITY_MAX_SPAN) return NSFF_ERR_INVALID;
-    if (!not_negative(a->min_parallax)) return NSFF_ERR_INVALID;
+    if (!bounded_not_negative(a->min_parallax)) return NSFF_ERR_INVALID;
     if (!a->flow_fw || !a->flow_bw || !a->Pm || !a->n || !a->c) return NSFF_ERR_NULL;
     if (a->counts && !a->scratch) return NSFF_ERR_NULL;
     if (a->counts && a->scratch_bytes < nsff_disparity_span_scratch_bytes(a->n_frames, a->H, a->W)) return NSFF_ERR_INVALID;
