@@ -1259,6 +1259,52 @@ def _dptr(t, dtype, what):
     return t.data_ptr()
 
 
+# ---- the frame kernels' argument structs are filled by the three helpers below
+_F32, _F64, _U8, _I32, _I64 = torch.float32, torch.float64, torch.uint8, torch.int32, torch.int64
+_MASK = "uint8, or bool taken as its uint8 view"          # a row's dtype
+
+
+def _bind(a, who, dev, *rows):
+    """Device pointers into the struct `a`, in the order given.  A row is (field, tensor, dtype, numel[, member[, index]]): a None
+    tensor is skipped; any other must be a contiguous GPU tensor of `dtype` (_MASK: uint8 or bool) with `numel` elements on `dev`,
+    and its pointer goes to a.<field> -- or to a.<member> / a.<member>[index], where `field` is the tensor's name in a refusal.
+    numel None is a workspace: any size, which goes to a.<field>_bytes."""
+    for row in rows:
+        t = row[1]
+        if t is None:
+            continue
+        field, dtype, numel = row[0], row[2], row[3]
+        if dtype is _MASK:
+            t, dtype = (t.view(torch.uint8) if t.dtype == torch.bool else t), torch.uint8
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+            _dptr(t, dtype, f"{who}: {field}")                     # raises and says which; a good tensor costs no formatting
+        if numel is None:
+            numel = t.numel()
+            setattr(a, field + "_bytes", numel)
+        if t.numel() != numel or t.device != dev:
+            raise RuntimeError(f"{who}: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
+        if len(row) == 4:
+            setattr(a, field, t.data_ptr())
+        elif len(row) == 5:
+            setattr(a, row[4], t.data_ptr())
+        else:
+            getattr(a, row[4])[row[5]] = t.data_ptr()
+
+
+def _scratch(scratch, wanted, dev, nbytes, *dims, zeroed=True):
+    """The caller's scratch as it is; without one and where `wanted`, a fresh one of nbytes(*dims) bytes (16 at least) -- zeroed for
+    the per-frame reductions, any content for a workspace -- else None.  The library is asked only then.  It is bound as the
+    workspace row ("scratch", ..., _U8, None)."""
+    if scratch is None and wanted:
+        return (torch.zeros if zeroed else torch.empty)(max(nbytes(*dims), 16), dtype=torch.uint8, device=dev)
+    return scratch
+
+
+def _launch(name, a, dev):
+    with torch.cuda.device(dev):
+        _check(getattr(load(), name)(C.byref(a), _stream()), name)
+
+
 def ssim_scratch_bytes(n_frames, H, W):
     return int(load().nsff_ssim_scratch_bytes(int(n_frames), int(H), int(W)))
 
@@ -1272,20 +1318,12 @@ def ssim(gt, pred, mask=None, map=None, mean_map=None, sums=None, scratch=None):
     if gt.dim() != 4 or gt.shape[-1] != 3 or pred.shape != gt.shape:
         raise RuntimeError(f"ssim: need (F, H, W, 3) image pairs of one shape, got {tuple(gt.shape)} and {tuple(pred.shape)}")
     F, H, W = (int(v) for v in gt.shape[:3])
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    if sums is not None and scratch is None:
-        scratch = torch.zeros(max(ssim_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=gt.device)
-    a = SsimArgs(n_frames=F, H=H, W=W, window=11, gt=_dptr(gt, torch.float32, "ssim: image_gt"),
-                 pred=_dptr(pred, torch.float32, "ssim: image_pred"), mask=_dptr(mask, torch.uint8, "ssim: mask"),
-                 map=_dptr(map, torch.float32, "ssim: map"), mean_map=_dptr(mean_map, torch.float32, "ssim: mean_map"),
-                 sums=_dptr(sums, torch.float64, "ssim: sums"), scratch=_dptr(scratch, torch.uint8, "ssim: scratch"),
-                 scratch_bytes=0 if scratch is None else scratch.numel())
-    for t, n in ((mask, F * H * W), (map, F * H * W * 3), (mean_map, F * H * W), (sums, F * 3)):
-        if t is not None and t.numel() != n:
-            raise RuntimeError(f"ssim: an output / mask has {t.numel()} elements, expected {n}")
-    with torch.cuda.device(gt.device):
-        _check(load().nsff_ssim(C.byref(a), _stream()), "nsff_ssim")
+    px, dev = F * H * W, gt.device
+    a = SsimArgs(n_frames=F, H=H, W=W, window=11)
+    _bind(a, "ssim", dev, ("image_gt", gt, _F32, px * 3, "gt"), ("image_pred", pred, _F32, px * 3, "pred"), ("mask", mask, _MASK, px),
+          ("map", map, _F32, px * 3), ("mean_map", mean_map, _F32, px), ("sums", sums, _F64, F * 3),
+          ("scratch", _scratch(scratch, sums is not None, dev, ssim_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_ssim", a, dev)
 
 
 LPIPS_MIN_SIZE = 31           # NSFF_LPIPS_MIN_SIZE
@@ -1336,23 +1374,17 @@ def lpips(packed, gt, pred, valid=None, map=None, sums=None, normalize=False, wo
         raise RuntimeError(f"lpips: need (F, H, W, 3) image pairs of one shape, got {tuple(gt.shape)} and {tuple(pred.shape)}")
     F, H, W = (int(v) for v in gt.shape[:3])
     lpips_dims(H, W)                                             # refuses an image that is too small by name
-    if valid is not None and valid.dtype == torch.bool:
-        valid = valid.view(torch.uint8)
+    px, dev = F * H * W, gt.device
     need = lpips_workspace_bytes(F, H, W)
     if need == 0:
         raise RuntimeError(f"lpips: {F} frames of {H} x {W} are outside what one call takes (1 .. 32767 frames, H * W < 2^31)")
     if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=gt.device)
-    a = LpipsArgs(n_frames=F, H=H, W=W, normalize=int(bool(normalize)), gt=_dptr(gt, torch.float32, "lpips: image_gt"),
-                  pred=_dptr(pred, torch.float32, "lpips: image_pred"), valid=_dptr(valid, torch.uint8, "lpips: valid"),
-                  packed=_dptr(packed, torch.float32, "lpips: packed weights"), map=_dptr(map, torch.float32, "lpips: map"),
-                  sums=_dptr(sums, torch.float64, "lpips: sums"), workspace=_dptr(workspace, torch.uint8, "lpips: workspace"),
-                  workspace_bytes=workspace.numel())
-    for t, n in ((valid, F * H * W), (map, F * H * W), (sums, F * 3)):
-        if t is not None and t.numel() != n:
-            raise RuntimeError(f"lpips: an output / mask has {t.numel()} elements, expected {n}")
-    with torch.cuda.device(gt.device):
-        _check(load().nsff_lpips(C.byref(a), _stream()), "nsff_lpips")
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    a = LpipsArgs(n_frames=F, H=H, W=W, normalize=int(bool(normalize)))
+    _bind(a, "lpips", dev, ("image_gt", gt, _F32, px * 3, "gt"), ("image_pred", pred, _F32, px * 3, "pred"), ("valid", valid, _MASK, px),
+          ("packed weights", packed, _F32, packed.numel(), "packed"), ("map", map, _F32, px), ("sums", sums, _F64, F * 3),
+          ("workspace", workspace, _U8, None))
+    _launch("nsff_lpips", a, dev)
 
 
 def frame_finish_scratch_bytes(n_frames, H, W):
@@ -1369,24 +1401,14 @@ def frame_finish(rgb, gt=None, valid=None, depth=None, lut=None, rgb_clipped=Non
     if rgb.dim() != 4 or rgb.shape[-1] != 3:
         raise RuntimeError(f"frame_finish: need (F, H, W, 3) frames, got {tuple(rgb.shape)}")
     F, H, W = (int(v) for v in rgb.shape[:3])
-    if valid is not None and valid.dtype == torch.bool:
-        valid = valid.view(torch.uint8)
-    if (sums is not None or depth_range is not None) and scratch is None:
-        scratch = torch.zeros(max(frame_finish_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=rgb.device)
-    given = dict(rgb=rgb, gt=gt, valid=valid, depth=depth, lut=lut, rgb_clipped=rgb_clipped, rgb_u8=rgb_u8, sums=sums,
-                 depth_range=depth_range, depth_u8=depth_u8, depth_rgb_u8=depth_rgb_u8)
-    dtypes = dict(rgb=torch.float32, gt=torch.float32, depth=torch.float32, rgb_clipped=torch.float32, sums=torch.float64,
-                  depth_range=torch.float32)
-    sizes = dict(rgb=F * H * W * 3, gt=F * H * W * 3, valid=F * H * W, depth=F * H * W, lut=768, rgb_clipped=F * H * W * 3,
-                 rgb_u8=F * H * W * 3, sums=F * 3, depth_range=F * 2, depth_u8=F * H * W, depth_rgb_u8=F * H * W * 3)
-    a = FrameFinishArgs(n_frames=F, H=H, W=W, scratch=_dptr(scratch, torch.uint8, "frame_finish: scratch"),
-                        scratch_bytes=0 if scratch is None else scratch.numel())
-    for name, t in given.items():
-        if t is not None and (t.numel() != sizes[name] or t.device != rgb.device):
-            raise RuntimeError(f"frame_finish: {name} has {t.numel()} elements on {t.device}, expected {sizes[name]} on {rgb.device}")
-        setattr(a, name, _dptr(t, dtypes.get(name, torch.uint8), f"frame_finish: {name}"))
-    with torch.cuda.device(rgb.device):
-        _check(load().nsff_frame_finish(C.byref(a), _stream()), "nsff_frame_finish")
+    px, dev = F * H * W, rgb.device
+    a = FrameFinishArgs(n_frames=F, H=H, W=W)
+    scratch = _scratch(scratch, sums is not None or depth_range is not None, dev, frame_finish_scratch_bytes, F, H, W)
+    _bind(a, "frame_finish", dev, ("scratch", scratch, _U8, None), ("rgb", rgb, _F32, px * 3), ("gt", gt, _F32, px * 3), ("valid", valid, _MASK, px),
+          ("depth", depth, _F32, px), ("lut", lut, _U8, 768), ("rgb_clipped", rgb_clipped, _F32, px * 3), ("rgb_u8", rgb_u8, _U8, px * 3),
+          ("sums", sums, _F64, F * 3), ("depth_range", depth_range, _F32, F * 2), ("depth_u8", depth_u8, _U8, px),
+          ("depth_rgb_u8", depth_rgb_u8, _U8, px * 3))
+    _launch("nsff_frame_finish", a, dev)
 
 
 def val_panels_scratch_bytes(n_frames, H, W):
@@ -1407,24 +1429,17 @@ def val_panels(F, H, W, pred, gt=None, depth=None, transient_alpha=None, static_
     F, H, W = int(F), int(H), int(W)
     require_gpu_tensor(pred, "val_panels: pred")
     dev, n = pred.device, F * H * W
-    if scratch is None:
-        scratch = torch.zeros(max(val_panels_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
-    given = dict(gt=gt, pred=pred, depth=depth, transient_alpha=transient_alpha, static_rgb=static_rgb, static_depth=static_depth,
-                 mask=mask, disp=disp, ssim_loss=ssim_loss, lut_depth=lut_depth, lut_mask=lut_mask, ranges=ranges, grid_u8=grid_u8,
-                 rmse_u8=rmse_u8, ssim_u8=ssim_u8, rmse_blend_u8=rmse_blend_u8, ssim_blend_u8=ssim_blend_u8)
     n_tiles = 3 + (3 if transient_alpha is not None else 0) + (mask is not None) + (disp is not None)
     GH, GW = panel_grid_shape(H, W, n_tiles)
-    sizes = dict(gt=n * 3, pred=n * 3, depth=n, transient_alpha=n, static_rgb=n * 3, static_depth=n, mask=n, disp=n, ssim_loss=n * 3,
-                 lut_depth=768, lut_mask=768, ranges=F * 10, grid_u8=F * GH * GW * 3, rmse_u8=n, ssim_u8=n, rmse_blend_u8=n * 3,
-                 ssim_blend_u8=n * 3)
-    a = ValPanelsArgs(n_frames=F, H=H, W=W, scratch=_dptr(scratch, torch.uint8, "val_panels: scratch"), scratch_bytes=scratch.numel())
-    for name, t in given.items():
-        if t is not None and (t.numel() != sizes[name] or t.device != dev):
-            raise RuntimeError(f"val_panels: {name} has {t.numel()} elements on {t.device}, expected {sizes[name]} on {dev}")
-        fp32 = name in _PANEL_IN or name == "ranges"
-        setattr(a, name, _dptr(t, torch.float32 if fp32 else torch.uint8, f"val_panels: {name}"))
-    with torch.cuda.device(dev):
-        _check(load().nsff_val_panels(C.byref(a), _stream()), "nsff_val_panels")
+    a = ValPanelsArgs(n_frames=F, H=H, W=W)
+    _bind(a, "val_panels", dev, ("scratch", _scratch(scratch, True, dev, val_panels_scratch_bytes, F, H, W), _U8, None),
+          ("gt", gt, _F32, n * 3), ("pred", pred, _F32, n * 3), ("depth", depth, _F32, n),
+          ("transient_alpha", transient_alpha, _F32, n), ("static_rgb", static_rgb, _F32, n * 3), ("static_depth", static_depth, _F32, n),
+          ("mask", mask, _F32, n), ("disp", disp, _F32, n), ("ssim_loss", ssim_loss, _F32, n * 3), ("lut_depth", lut_depth, _U8, 768),
+          ("lut_mask", lut_mask, _U8, 768), ("ranges", ranges, _F32, F * 10), ("grid_u8", grid_u8, _U8, F * GH * GW * 3),
+          ("rmse_u8", rmse_u8, _U8, n), ("ssim_u8", ssim_u8, _U8, n), ("rmse_blend_u8", rmse_blend_u8, _U8, n * 3),
+          ("ssim_blend_u8", ssim_blend_u8, _U8, n * 3))
+    _launch("nsff_val_panels", a, dev)
 
 
 def flow_maps_scratch_bytes(n_frames, H, W):
@@ -1447,41 +1462,17 @@ def flow_maps(F, H, W, xyz=(None, None), K4=None, Ps=None, ts=None, max_t=0, flo
     first = next((t for t in list(xyz) + list(flow) + list(gt) if t is not None), None)
     require_gpu_tensor(first, "flow_maps: points / flow")
     dev = first.device
-
-    def put(field, t, dtype, numel, what, index=None):
-        if t is None:
-            return
-        ptr = _dptr(t, dtype, f"flow_maps: {what}")
-        if t.numel() != numel or t.device != dev:
-            raise RuntimeError(f"flow_maps: {what} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
-        if index is None:
-            setattr(a, field, ptr)
-        else:
-            getattr(a, field)[index] = ptr
-    for d, tag in enumerate(("fw", "bw")):
-        put("xyz", xyz[d], torch.float32, n * 3, f"xyz_{tag}", d)
-        put("flow", flow[d], torch.float32, n * 2, f"flow_{tag}", d)
-        put("gt", gt[d], torch.float32, n * 2, f"gt_{tag}", d)
-        put("image", image[d], torch.uint8, n * 3, f"image_{tag}", d)
-        put("gt_image", gt_image[d], torch.uint8, n * 3, f"gt_image_{tag}", d)
     if Ps is not None:
         a.n_poses = int(Ps.numel() // 12)
-        put("Ps", Ps, torch.float32, a.n_poses * 12, "Ps")
-    put("ts", ts, torch.int32, F, "ts")
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    put("mask", mask, torch.uint8, n, "mask")
-    put("epe_sums", epe_sums, torch.float64, F * 6, "epe_sums")
-    put("epe_counts", epe_counts, torch.int64, F * 6, "epe_counts")
-    put("maxrad", maxrad, torch.float32, F * 4, "maxrad")
-    put("scale", scale, torch.float32, F * 4, "scale")
-    if (epe_sums is not None or maxrad is not None) and scratch is None:
-        scratch = torch.zeros(max(flow_maps_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
-    if scratch is not None:
-        put("scratch", scratch, torch.uint8, scratch.numel(), "scratch")
-        a.scratch_bytes = scratch.numel()
-    with torch.cuda.device(dev):
-        _check(load().nsff_flow_maps(C.byref(a), _stream()), "nsff_flow_maps")
+    pairs = [row for d, tag in enumerate(("fw", "bw")) for row in (
+        (f"xyz_{tag}", xyz[d], _F32, n * 3, "xyz", d), (f"flow_{tag}", flow[d], _F32, n * 2, "flow", d),
+        (f"gt_{tag}", gt[d], _F32, n * 2, "gt", d), (f"image_{tag}", image[d], _U8, n * 3, "image", d),
+        (f"gt_image_{tag}", gt_image[d], _U8, n * 3, "gt_image", d))]
+    _bind(a, "flow_maps", dev, *pairs, ("Ps", Ps, _F32, a.n_poses * 12), ("ts", ts, _I32, F), ("mask", mask, _MASK, n),
+          ("epe_sums", epe_sums, _F64, F * 6), ("epe_counts", epe_counts, _I64, F * 6), ("maxrad", maxrad, _F32, F * 4),
+          ("scale", scale, _F32, F * 4),
+          ("scratch", _scratch(scratch, epe_sums is not None or maxrad is not None, dev, flow_maps_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_flow_maps", a, dev)
 
 
 def track_step(n_rows, pts_per_row, direction, max_t, xyz_in, t_in, alive_in, raw=None, xyz_out=None, t_out=None, alive_out=None,
@@ -1496,7 +1487,7 @@ def track_step(n_rows, pts_per_row, direction, max_t, xyz_in, t_in, alive_in, ra
     a.t_in, a.t_out = _dptr(t_in, torch.int32, "t_in"), _dptr(t_out, torch.int32, "t_out")
     a.alive_in, a.alive_out = _dptr(alive_in, torch.uint8, "alive_in"), _dptr(alive_out, torch.uint8, "alive_out")
     a.Ps, a.uv, a.depth = _ptr(Ps), _ptr(uv), _ptr(depth)
-    _check(load().nsff_track_step(C.byref(a), _stream()), "nsff_track_step")
+    _launch("nsff_track_step", a, xyz_in.device)
 
 
 def track_draw_scratch_bytes(H, W):
@@ -1509,7 +1500,7 @@ def track_draw(H, W, n_steps, n_tracks, uv, ok, image, lut, out, scratch):
     a.uv, a.ok = _ptr(uv), _dptr(ok, torch.uint8, "ok")
     a.image, a.lut, a.out = _dptr(image, torch.uint8, "image"), _dptr(lut, torch.uint8, "lut"), _dptr(out, torch.uint8, "out")
     a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "scratch"), int(scratch.numel())
-    _check(load().nsff_track_draw(C.byref(a), _stream()), "nsff_track_draw")
+    _launch("nsff_track_draw", a, image.device)
 
 
 def motion_maps_scratch_bytes(n_frames, H, W):
@@ -1527,22 +1518,11 @@ def motion_maps(flows_fw, flows_bw, Fm=None, alpha=0.01, beta=0.5, threshold=1.0
     n, dev = F * H * W, flows_fw.device
     a = MotionMapsArgs(n_frames=F, H=H, W=W, epipolar=int(Fm is not None), alpha=float(alpha), beta=float(beta),
                        threshold=float(threshold))
-    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, n * 2), ("flow_bw", flows_bw, torch.float32, n * 2),
-                                   ("Fm", Fm, torch.float32, F * 18), ("err", err, torch.float32, n * 2),
-                                   ("valid", valid, torch.uint8, n * 2), ("raw", raw, torch.uint8, n),
-                                   ("counts", counts, torch.int64, F * 5), ("err_sums", err_sums, torch.float64, F * 2)):
-        if t is None:
-            continue
-        ptr = _dptr(t, dtype, f"motion_maps: {field}")
-        if t.numel() != numel or t.device != dev:
-            raise RuntimeError(f"motion_maps: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
-        setattr(a, field, ptr)
-    if counts is not None and scratch is None:
-        scratch = torch.zeros(max(motion_maps_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
-    if scratch is not None:
-        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "motion_maps: scratch"), scratch.numel()
-    with torch.cuda.device(dev):
-        _check(load().nsff_motion_maps(C.byref(a), _stream()), "nsff_motion_maps")
+    _bind(a, "motion_maps", dev, ("flow_fw", flows_fw, _F32, n * 2), ("flow_bw", flows_bw, _F32, n * 2), ("Fm", Fm, _F32, F * 18),
+          ("err", err, _F32, n * 2), ("valid", valid, _U8, n * 2), ("raw", raw, _U8, n), ("counts", counts, _I64, F * 5),
+          ("err_sums", err_sums, _F64, F * 2),
+          ("scratch", _scratch(scratch, counts is not None, dev, motion_maps_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_motion_maps", a, dev)
 
 
 def mask_erode(src, dst, k, zero_counts=None, scratch=None):
@@ -1550,16 +1530,11 @@ def mask_erode(src, dst, k, zero_counts=None, scratch=None):
     pixels of each eroded frame.  scratch as for motion_maps."""
     require_gpu_tensor(src, "mask_erode: src")
     F, H, W = (int(v) for v in src.shape)
-    a = MaskErodeArgs(n_frames=F, H=H, W=W, k=int(k), src=_dptr(src, torch.uint8, "mask_erode: src"),
-                      dst=_dptr(dst, torch.uint8, "mask_erode: dst"), zero_counts=_dptr(zero_counts, torch.int64, "mask_erode: zero_counts"))
-    if dst.numel() != src.numel() or dst.device != src.device or (zero_counts is not None and zero_counts.numel() != F):
-        raise RuntimeError(f"mask_erode: dst / zero_counts do not go with {tuple(src.shape)} images on {src.device}")
-    if zero_counts is not None and scratch is None:
-        scratch = torch.zeros(max(motion_maps_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=src.device)
-    if scratch is not None:
-        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "mask_erode: scratch"), scratch.numel()
-    with torch.cuda.device(src.device):
-        _check(load().nsff_mask_erode(C.byref(a), _stream()), "nsff_mask_erode")
+    px, dev = F * H * W, src.device
+    a = MaskErodeArgs(n_frames=F, H=H, W=W, k=int(k))
+    _bind(a, "mask_erode", dev, ("src", src, _U8, px), ("dst", dst, _U8, px), ("zero_counts", zero_counts, _I64, F),
+          ("scratch", _scratch(scratch, zero_counts is not None, dev, motion_maps_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_mask_erode", a, dev)
 
 
 # ---- TV-L1 optical flow (csrc/optflow.hip).  Planes are contiguous fp32 (n, H, W) GPU tensors; the stage calls return their output.
@@ -1642,8 +1617,7 @@ def optflow_iterate(consts, state, iters, lam=0.15, theta=0.3, tau=0.25, fused=T
     a = OptflowIterArgs(n_pairs=P, H=H, W=W, iters=int(iters), fused=int(bool(fused)), tile=int(tile), k=int(k), lam=float(lam),
                         theta=float(theta), tau=float(tau), consts=consts.data_ptr())
     a.state[0], a.state[1] = state.data_ptr(), other.data_ptr()
-    with torch.cuda.device(state.device):
-        _check(load().nsff_optflow_iterate(C.byref(a), _stream()), "nsff_optflow_iterate")
+    _launch("nsff_optflow_iterate", a, state.device)
     per_launch = (int(k) or OPTFLOW_K) if fused else 1
     return (state, other)[optflow_result_slot(iters, per_launch)]
 
@@ -1667,14 +1641,11 @@ def optflow(images0, images1, flow, levels=5, warps=5, iters=30, lam=0.15, theta
     dev = images0.device
     if images1.shape != images0.shape or images1.device != dev or tuple(flow.shape) != (P, H, W, 2) or flow.device != dev:
         raise RuntimeError(f"optflow: images1 {tuple(images1.shape)} / flow {tuple(flow.shape)} do not go with images0 {tuple(images0.shape)} on {dev}")
-    if scratch is None:
-        scratch = torch.empty(max(optflow_scratch_bytes(P, H, W, levels), 16), dtype=torch.uint8, device=dev)
     a = OptflowArgs(n_pairs=P, H=H, W=W, channels=channels, levels=int(levels), warps=int(warps), iters=int(iters), median=int(bool(median)),
                     fused=int(bool(fused)), tile=int(tile), k=int(k), lam=float(lam), theta=float(theta), tau=float(tau),
-                    images0=p0, images1=p1, flow=_dptr(flow, torch.float32, "optflow: flow"),
-                    scratch=_dptr(scratch, torch.uint8, "optflow: scratch"), scratch_bytes=scratch.numel())
-    with torch.cuda.device(dev):
-        _check(load().nsff_optflow(C.byref(a), _stream()), "nsff_optflow")
+                    images0=p0, images1=p1, flow=_dptr(flow, torch.float32, "optflow: flow"))
+    _bind(a, "optflow", dev, ("scratch", _scratch(scratch, True, dev, optflow_scratch_bytes, P, H, W, levels, zeroed=False), _U8, None))
+    _launch("nsff_optflow", a, dev)
     return flow
 
 
@@ -1687,16 +1658,8 @@ def flow_median(flow, grey, out, valid=None, radius=7, sigma_i=12.75, sigma_s=7.
     P, H, W = (int(v) for v in flow.shape[:3])
     px, dev = P * H * W, flow.device
     a = FlowMedianArgs(n_pairs=P, H=H, W=W, radius=int(radius), sigma_i=float(sigma_i), sigma_s=float(sigma_s), tiled=int(bool(tiled)))
-    for field, t, dtype, numel in (("flow", flow, torch.float32, px * 2), ("grey", grey, torch.float32, px),
-                                   ("valid", valid, torch.uint8, px), ("out", out, torch.float32, px * 2)):
-        if t is None:
-            continue
-        ptr = _dptr(t, dtype, f"flow_median: {field}")
-        if t.numel() != numel or t.device != dev:
-            raise RuntimeError(f"flow_median: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
-        setattr(a, field, ptr)
-    with torch.cuda.device(dev):
-        _check(load().nsff_flow_median(C.byref(a), _stream()), "nsff_flow_median")
+    _bind(a, "flow_median", dev, ("flow", flow, _F32, px * 2), ("grey", grey, _F32, px), ("valid", valid, _U8, px), ("out", out, _F32, px * 2))
+    _launch("nsff_flow_median", a, dev)
     return out
 
 
@@ -1714,21 +1677,10 @@ def disparity_sparse(flows_fw, flows_bw, Pm, valid=None, masks=None, min_paralla
     px, dev = F * H * W, flows_fw.device
     n, c = (torch.empty(F, H, W, dtype=torch.float32, device=dev) for _ in range(2))
     a = DisparitySparseArgs(n_frames=F, H=H, W=W, min_parallax=float(min_parallax), n=n.data_ptr(), c=c.data_ptr())
-    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, px * 2), ("flow_bw", flows_bw, torch.float32, px * 2),
-                                   ("Pm", Pm, torch.float32, F * 24), ("valid", valid, torch.uint8, px * 2),
-                                   ("masks", masks, torch.uint8, px), ("counts", counts, torch.int64, F)):
-        if t is None:
-            continue
-        ptr = _dptr(t, dtype, f"disparity_sparse: {field}")
-        if t.numel() != numel or t.device != dev:
-            raise RuntimeError(f"disparity_sparse: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
-        setattr(a, field, ptr)
-    if counts is not None and scratch is None:
-        scratch = torch.zeros(max(disparity_sparse_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
-    if scratch is not None:
-        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "disparity_sparse: scratch"), scratch.numel()
-    with torch.cuda.device(dev):
-        _check(load().nsff_disparity_sparse(C.byref(a), _stream()), "nsff_disparity_sparse")
+    _bind(a, "disparity_sparse", dev, ("flow_fw", flows_fw, _F32, px * 2), ("flow_bw", flows_bw, _F32, px * 2), ("Pm", Pm, _F32, F * 24),
+          ("valid", valid, _U8, px * 2), ("masks", masks, _U8, px), ("counts", counts, _I64, F),
+          ("scratch", _scratch(scratch, counts is not None, dev, disparity_sparse_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_disparity_sparse", a, dev)
     return n, c
 
 
@@ -1750,23 +1702,11 @@ def disparity_span(flows_fw, flows_bw, Pm, span, valid=None, masks=None, min_par
     if votes is None:
         votes = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
     a = DisparitySpanArgs(n_frames=F, H=H, W=W, span=span, min_parallax=float(min_parallax))
-    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, px * 2), ("flow_bw", flows_bw, torch.float32, px * 2),
-                                   ("n", n, torch.float32, px), ("c", c, torch.float32, px),
-                                   ("Pm", Pm, torch.float32, F * 24 * span), ("valid", valid, torch.uint8, px * 2),
-                                   ("masks", masks, torch.uint8, px), ("votes", votes, torch.uint8, px),
-                                   ("counts", counts, torch.int64, F)):
-        if t is None:
-            continue
-        ptr = _dptr(t, dtype, f"disparity_span: {field}")
-        if t.numel() != numel or t.device != dev:
-            raise RuntimeError(f"disparity_span: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
-        setattr(a, field, ptr)
-    if counts is not None and scratch is None:
-        scratch = torch.zeros(max(disparity_span_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
-    if scratch is not None:
-        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "disparity_span: scratch"), scratch.numel()
-    with torch.cuda.device(dev):
-        _check(load().nsff_disparity_span(C.byref(a), _stream()), "nsff_disparity_span")
+    _bind(a, "disparity_span", dev, ("flow_fw", flows_fw, _F32, px * 2), ("flow_bw", flows_bw, _F32, px * 2), ("n", n, _F32, px),
+          ("c", c, _F32, px), ("Pm", Pm, _F32, F * 24 * span), ("valid", valid, _U8, px * 2), ("masks", masks, _U8, px),
+          ("votes", votes, _U8, px), ("counts", counts, _I64, F),
+          ("scratch", _scratch(scratch, counts is not None, dev, disparity_span_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_disparity_span", a, dev)
     return n, c, votes
 
 
@@ -1787,23 +1727,11 @@ def motion_span(flows_fw, flows_bw, Fm, hop_scale, span, valid=None, threshold=1
     if raw is None:
         raw = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
     a = MotionSpanArgs(n_frames=F, H=H, W=W, span=span, threshold=float(threshold))
-    for field, t, dtype, numel in (("flow_fw", flows_fw, torch.float32, px * 2), ("flow_bw", flows_bw, torch.float32, px * 2),
-                                   ("Fm", Fm, torch.float32, F * 18 * span), ("hop_scale", hop_scale, torch.float32, span),
-                                   ("valid", valid, torch.uint8, px * 2), ("err", err, torch.float32, px * 2),
-                                   ("hops", hops, torch.uint8, px * 2), ("raw", raw, torch.uint8, px),
-                                   ("counts", counts, torch.int64, F * 3)):
-        if t is None:
-            continue
-        ptr = _dptr(t, dtype, f"motion_span: {field}")
-        if t.numel() != numel or t.device != dev:
-            raise RuntimeError(f"motion_span: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
-        setattr(a, field, ptr)
-    if counts is not None and scratch is None:
-        scratch = torch.zeros(max(motion_span_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
-    if scratch is not None:
-        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "motion_span: scratch"), scratch.numel()
-    with torch.cuda.device(dev):
-        _check(load().nsff_motion_span(C.byref(a), _stream()), "nsff_motion_span")
+    _bind(a, "motion_span", dev, ("flow_fw", flows_fw, _F32, px * 2), ("flow_bw", flows_bw, _F32, px * 2), ("Fm", Fm, _F32, F * 18 * span),
+          ("hop_scale", hop_scale, _F32, span), ("valid", valid, _U8, px * 2), ("err", err, _F32, px * 2), ("hops", hops, _U8, px * 2),
+          ("raw", raw, _U8, px), ("counts", counts, _I64, F * 3),
+          ("scratch", _scratch(scratch, counts is not None, dev, motion_span_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_motion_span", a, dev)
     return raw
 
 
@@ -1817,22 +1745,10 @@ def mask_propagate(src, flows_fw, flows_bw, reach, valid=None, dst=None, hits=No
     if dst is None:
         dst = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
     a = MaskPropagateArgs(n_frames=F, H=H, W=W, reach=int(reach))
-    for field, t, dtype, numel in (("src", src, torch.uint8, px), ("flow_fw", flows_fw, torch.float32, px * 2),
-                                   ("flow_bw", flows_bw, torch.float32, px * 2), ("valid", valid, torch.uint8, px * 2),
-                                   ("dst", dst, torch.uint8, px), ("hits", hits, torch.uint8, px),
-                                   ("zero_counts", zero_counts, torch.int64, F)):
-        if t is None:
-            continue
-        ptr = _dptr(t, dtype, f"mask_propagate: {field}")
-        if t.numel() != numel or t.device != dev:
-            raise RuntimeError(f"mask_propagate: {field} has {t.numel()} elements on {t.device}, expected {numel} on {dev}")
-        setattr(a, field, ptr)
-    if zero_counts is not None and scratch is None:
-        scratch = torch.zeros(max(motion_span_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
-    if scratch is not None:
-        a.scratch, a.scratch_bytes = _dptr(scratch, torch.uint8, "mask_propagate: scratch"), scratch.numel()
-    with torch.cuda.device(dev):
-        _check(load().nsff_mask_propagate(C.byref(a), _stream()), "nsff_mask_propagate")
+    _bind(a, "mask_propagate", dev, ("src", src, _U8, px), ("flow_fw", flows_fw, _F32, px * 2), ("flow_bw", flows_bw, _F32, px * 2),
+          ("valid", valid, _U8, px * 2), ("dst", dst, _U8, px), ("hits", hits, _U8, px), ("zero_counts", zero_counts, _I64, F),
+          ("scratch", _scratch(scratch, zero_counts is not None, dev, motion_span_scratch_bytes, F, H, W), _U8, None))
+    _launch("nsff_mask_propagate", a, dev)
     return dst
 
 
@@ -1888,8 +1804,7 @@ def disparity_relax(d, n, c, grey, iters, lam=8.0, sigma=12.75, fused=False, til
     a = DisparityRelaxArgs(n_frames=F, H=H, W=W, iters=int(iters), fused=int(bool(fused)), tile=int(tile), k=int(k), lam=float(lam),
                            sigma=float(sigma), n=n.data_ptr(), c=c.data_ptr(), grey=grey.data_ptr())
     a.state[0], a.state[1] = d.data_ptr(), other.data_ptr()
-    with torch.cuda.device(d.device):
-        _check(load().nsff_disparity_relax(C.byref(a), _stream()), "nsff_disparity_relax")
+    _launch("nsff_disparity_relax", a, d.device)
     per_launch = (int(k) or DISPARITY_K) if fused else 1
     return (d, other)[disparity_result_slot(iters, per_launch)]
 
@@ -1906,14 +1821,11 @@ def disparity_dense(n, c, grey, disps, levels=3, iters=30, lam=8.0, sigma=12.75,
     """nsff_disparity_dense: disps (F, H, W) fp32 from the planes n, c and the guide grey.  scratch: a uint8 tensor of
     disparity_dense_scratch_bytes() bytes, any content (a fresh one when None)."""
     F, H, W = _same_planes("disparity_dense", c, n=n, grey=grey, disps=disps)
-    dev = c.device
-    if scratch is None:
-        scratch = torch.empty(max(disparity_dense_scratch_bytes(F, H, W), 16), dtype=torch.uint8, device=dev)
     a = DisparityDenseArgs(n_frames=F, H=H, W=W, levels=int(levels), iters=int(iters), fused=int(bool(fused)), tile=int(tile), k=int(k),
-                           lam=float(lam), sigma=float(sigma), n=n.data_ptr(), c=c.data_ptr(), grey=grey.data_ptr(), disps=disps.data_ptr(),
-                           scratch=_dptr(scratch, torch.uint8, "disparity_dense: scratch"), scratch_bytes=scratch.numel())
-    with torch.cuda.device(dev):
-        _check(load().nsff_disparity_dense(C.byref(a), _stream()), "nsff_disparity_dense")
+                           lam=float(lam), sigma=float(sigma), n=n.data_ptr(), c=c.data_ptr(), grey=grey.data_ptr(), disps=disps.data_ptr())
+    dev = c.device
+    _bind(a, "disparity_dense", dev, ("scratch", _scratch(scratch, True, dev, disparity_dense_scratch_bytes, F, H, W, zeroed=False), _U8, None))
+    _launch("nsff_disparity_dense", a, dev)
     return disps
 
 
@@ -1962,8 +1874,7 @@ def ray_records(K4, frame_table, images, disps, masks, flow_fw, flow_bw, near, f
                       flow_bw=_dptr(flow_bw, torch.float32, "ray_records: flows_bw"),
                       frame_table=_dptr(frame_table, torch.float32, "ray_records: frame table"),
                       records=_dptr(records, torch.float32, "ray_records: out"))
-    with torch.cuda.device(records.device):
-        _check(load().nsff_ray_records(C.byref(a), _stream()), "nsff_ray_records")
+    _launch("nsff_ray_records", a, records.device)
 
 
 def resize_ksize(filter, n_in, n_out):
@@ -2010,8 +1921,7 @@ def frame_resize(filter, src, dst, x_table, y_table, ratio=(1.0, 1.0)):
         setattr(a, f"{axis}_count", _dptr(count, torch.int32, f"frame_resize: {axis}_count"))
         setattr(a, f"{axis}_weights", _dptr(weights, wdtype, f"frame_resize: {axis}_weights"))
         setattr(a, f"ksize_{axis}", 1 if weights is None else int(weights.shape[1]))
-    with torch.cuda.device(src.device):
-        _check(load().nsff_frame_resize(C.byref(a), _stream()), "nsff_frame_resize")
+    _launch("nsff_frame_resize", a, src.device)
 
 
 def scene_scale_work_bytes(n_frames, n_points, H, W):
@@ -2051,8 +1961,7 @@ def scene_scale(points, vis, w2c, K, disps, disp_rank, want_pix=False, work=None
                        disp_os=_dptr(disp_os, torch.float32, "scene_scale: disp_os"),
                        depth_os=_dptr(depth_os, torch.float64, "scene_scale: depth_os"), pix=_dptr(pix, torch.int32, "scene_scale: pix"),
                        work=_dptr(work, torch.uint8, "scene_scale: work"), work_bytes=0 if work is None else work.numel())
-    with torch.cuda.device(dev):
-        _check(load().nsff_scene_scale(C.byref(a), _stream()), "nsff_scene_scale")
+    _launch("nsff_scene_scale", a, dev)
     return stats, disp_os, depth_os, pix
 
 

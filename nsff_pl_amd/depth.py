@@ -51,9 +51,7 @@ GREY_SIGMA = 12.75                            # 0.05 of the 0..255 scale of optf
 
 
 def _check_span(who, span):
-    if isinstance(span, bool) or not isinstance(span, (int, np.integer)) or not 1 <= span <= _lib.DISPARITY_MAX_SPAN:
-        raise ValueError(f"{who}: span must be an integer from 1 to {_lib.DISPARITY_MAX_SPAN}, got {span!r}")
-    return int(span)
+    return motion._check_span(who, span, hi=_lib.DISPARITY_MAX_SPAN)
 
 
 def parallax_matrices(K, poses, rounded=True, span=1):
@@ -66,48 +64,15 @@ def parallax_matrices(K, poses, rounded=True, span=1):
     (:data:`nsff_pl_amd.motion.COINCIDENT`'s rule): the kernel reads a zero row as "no vote".  ``span`` > 1: (F, 2, span, 12), row
     k - 1 built for the neighbour n = f + k / f - k by the same formula and the same rules."""
     span = _check_span("parallax_matrices", span)
-    K, poses = motion._host(K), motion._host(poses)
-    if K.shape == (1, 3, 3):
-        K = K[0]
-    if K.shape != (3, 3):
-        raise RuntimeError(f"parallax_matrices: K must be (3,3) or (1,3,3), got {K.shape}")
-    if poses.ndim != 3 or poses.shape[1:] != (3, 4):
-        raise RuntimeError(f"parallax_matrices: poses must be (F,3,4) camera-to-world matrices, got {poses.shape}")
-    F = len(poses)
-    M = K @ np.diag([1.0, -1.0, -1.0]) @ np.linalg.inv(poses[:, :, :3])
-    M_inv = np.linalg.inv(M)
-    C = poses[:, :, 3]
+    F, pairs = motion.camera_pairs("parallax_matrices", K, poses, span)
     out = np.zeros((F, 2, span, 12))
-    for f in range(F):
-        for d, step in enumerate((+1, -1)):
-            for k in range(1, span + 1):
-                n = f + step * k
-                if not 0 <= n < F:
-                    break
-                base = C[f] - C[n]
-                if np.linalg.norm(base) <= motion.COINCIDENT * max(1.0, np.linalg.norm(C[f]), np.linalg.norm(C[n])):
-                    continue
-                row = np.concatenate([(M[n] @ M_inv[f]).ravel(), M[n] @ base])
-                if np.isfinite(row).all():
-                    out[f, d, k - 1] = row
+    for f, d, k, M_n, M_f_inv, base in pairs:
+        row = np.concatenate([(M_n @ M_f_inv).ravel(), M_n @ base])
+        if np.isfinite(row).all():
+            out[f, d, k - 1] = row
     if span == 1:
         out = out[:, :, 0]
     return torch.tensor(out, dtype=torch.float32) if rounded else out
-
-
-def _uint8_maps(t, shape, dev, who, what):
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{who}: {what}: need a tensor, got {type(t).__name__}")
-    if t.dtype == torch.bool:
-        t = t.to(torch.uint8)
-    if t.dtype != torch.uint8 or tuple(t.shape) != shape:
-        raise RuntimeError(f"{who}: {what}: need {shape} uint8, got {tuple(t.shape)} {t.dtype}")
-    _lib.require_gpu_tensor(t, f"{who}: {what}")
-    if t.device != dev:
-        raise RuntimeError(f"{who}: {what} is on {t.device}, the flows on {dev}")
-    return t.contiguous()
 
 
 def _check_dense(who, levels, iters, lam, sigma):
@@ -162,8 +127,8 @@ def _triangulate(who, flows_fw, flows_bw, K, poses, valid, masks, min_parallax, 
     Pm = parallax_matrices(K, poses, span=span)
     if Pm.shape[0] != F:
         raise RuntimeError(f"{who}: {F} frames of flow need {F} poses, got {Pm.shape[0]}")
-    valid = _uint8_maps(valid, (F, 2, H, W), dev, who, "valid")
-    masks = _uint8_maps(masks, (F, H, W), dev, who, "masks")
+    valid = motion._uint8_maps(who, "valid", valid, (F, 2, H, W), dev, take_bool=True)
+    masks = motion._uint8_maps(who, "masks", masks, (F, H, W), dev, take_bool=True)
     counts = torch.empty(F, dtype=torch.int64, device=dev)
     extra = {}
     if span == 1:
@@ -189,20 +154,6 @@ def default_route(n_frames, H, W):
 def scratch_bytes(n_frames, H, W):
     """The size of the ``scratch`` tensor (uint8) that :func:`densify` takes for this shape."""
     return _lib.disparity_dense_scratch_bytes(n_frames, H, W)
-
-
-def _guide(images_or_grey, shape, dev, who):
-    t = images_or_grey
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"{who}: images: need a tensor, got {type(t).__name__}")
-    colour = t.dtype == torch.uint8
-    if t.dtype not in (torch.uint8, torch.float32) or tuple(t.shape) != (shape + (3,) if colour else shape):
-        raise RuntimeError(f"{who}: images: need channels-last {shape + (3,)} uint8 frames or a grey {shape} float32 guide, got "
-                           f"{tuple(t.shape)} {t.dtype}")
-    _lib.require_gpu_tensor(t, f"{who}: images")
-    if t.device != dev:
-        raise RuntimeError(f"{who}: images are on {t.device}, the disparity on {dev}")
-    return _lib.optflow_grey(t.contiguous()) if colour else t.contiguous()
 
 
 def densify(sparse, conf, images_or_grey, levels=3, iters=30, lam=8.0, sigma=GREY_SIGMA, fused=None, scratch=None):
@@ -239,7 +190,7 @@ def _densify(who, n, c, images_or_grey, levels, iters, lam, sigma, fused, scratc
     top = _lib.disparity_levels(H, W)
     if levels > top:
         raise ValueError(f"{who}: levels must be an integer from 1 to {top} for {H} x {W} frames, got {levels}")
-    grey = _guide(images_or_grey, (F, H, W), c.device, who)
+    grey = motion._grey(motion._guide(who, images_or_grey, (F, H, W), c.device, "the disparity"))
     route, tile, k = default_route(F, H, W) if fused is None else (bool(fused), 0, 0)
     disps = torch.empty(F, H, W, dtype=torch.float32, device=c.device)
     return _lib.disparity_dense(n, c, grey, disps, levels=levels, iters=iters, lam=lam, sigma=sigma, fused=route, tile=tile, k=k,

@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .flow import _host
 
 UNKNOWN = _lib.FLOW_UNKNOWN
 ERODE_MAX_K = _lib.ERODE_MAX_K
@@ -42,8 +43,35 @@ MAX_SPAN, MAX_REACH = _lib.MOTION_MAX_SPAN, _lib.PROPAGATE_MAX_REACH
 COINCIDENT = 1e-12            # two camera centres closer than this times max(1, their norms) count as one
 
 
-def _host(x):
-    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
+def camera_pairs(who, K, poses, span):
+    """``(F, pairs)`` of a sequence: K (3,3) or (1,3,3), poses (F,3,4) camera-to-world, refused in ``who``'s name.  ``pairs`` yields
+    ``(f, d, k, M[n], M_inv[f], C[f] - C[n])`` in float64 for every frame f, direction d (0: n = f + k, 1: n = f - k) and
+    k = 1 .. span whose neighbour n exists and whose camera centres C are distinct (:data:`COINCIDENT`), with
+    ``M = K diag(1,-1,-1) R^-1``."""
+    K, poses = _host(K), _host(poses)
+    if K.shape == (1, 3, 3):
+        K = K[0]
+    if K.shape != (3, 3):
+        raise RuntimeError(f"{who}: K must be (3,3) or (1,3,3), got {K.shape}")
+    if poses.ndim != 3 or poses.shape[1:] != (3, 4):
+        raise RuntimeError(f"{who}: poses must be (F,3,4) camera-to-world matrices, got {poses.shape}")
+    F = len(poses)
+    M = K @ np.diag([1.0, -1.0, -1.0]) @ np.linalg.inv(poses[:, :, :3])
+    M_inv = np.linalg.inv(M)
+    C = poses[:, :, 3]
+
+    def pairs():
+        for f in range(F):
+            for d, s in enumerate((+1, -1)):
+                for k in range(1, span + 1):
+                    n = f + s * k
+                    if not 0 <= n < F:
+                        break
+                    base = C[f] - C[n]
+                    if np.linalg.norm(base) <= COINCIDENT * max(1.0, np.linalg.norm(C[f]), np.linalg.norm(C[n])):
+                        continue
+                    yield f, d, k, M[n], M_inv[f], base
+    return F, pairs()
 
 
 def fundamental_matrices(K, poses, rounded=True, span=1):
@@ -57,33 +85,15 @@ def fundamental_matrices(K, poses, rounded=True, span=1):
     ``span`` > 1: (F, 2, span, 3, 3), row k - 1 built for the neighbour n = f + k / f - k by the same formula and the same rules;
     row 0 has the bits of ``span=1``."""
     span = _check_span("fundamental_matrices", span)
-    K, poses = _host(K), _host(poses)
-    if K.shape == (1, 3, 3):
-        K = K[0]
-    if K.shape != (3, 3):
-        raise RuntimeError(f"fundamental_matrices: K must be (3,3) or (1,3,3), got {K.shape}")
-    if poses.ndim != 3 or poses.shape[1:] != (3, 4):
-        raise RuntimeError(f"fundamental_matrices: poses must be (F,3,4) camera-to-world matrices, got {poses.shape}")
-    F = len(poses)
-    M = K @ np.diag([1.0, -1.0, -1.0]) @ np.linalg.inv(poses[:, :, :3])
-    M_inv = np.linalg.inv(M)
-    C = poses[:, :, 3]
+    F, pairs = camera_pairs("fundamental_matrices", K, poses, span)
     out = np.zeros((F, 2, span, 3, 3))
-    for f in range(F):
-        for d, s in enumerate((+1, -1)):
-            for k in range(1, span + 1):
-                n = f + s * k
-                if not 0 <= n < F:
-                    continue
-                base = C[f] - C[n]
-                if np.linalg.norm(base) <= COINCIDENT * max(1.0, np.linalg.norm(C[f]), np.linalg.norm(C[n])):
-                    continue
-                e = M[n] @ base
-                cross = np.array([[0.0, -e[2], e[1]], [e[2], 0.0, -e[0]], [-e[1], e[0], 0.0]])
-                Fm = cross @ M[n] @ M_inv[f]
-                norm = np.linalg.norm(Fm)
-                if np.isfinite(norm) and norm > 0:
-                    out[f, d, k - 1] = Fm / norm
+    for f, d, k, M_n, M_f_inv, base in pairs:
+        e = M_n @ base
+        cross = np.array([[0.0, -e[2], e[1]], [e[2], 0.0, -e[0]], [-e[1], e[0], 0.0]])
+        Fm = cross @ M_n @ M_f_inv
+        norm = np.linalg.norm(Fm)
+        if np.isfinite(norm) and norm > 0:
+            out[f, d, k - 1] = Fm / norm
     if span == 1:
         out = out[:, :, 0]
     return torch.tensor(out, dtype=torch.float32) if rounded else out
@@ -104,6 +114,44 @@ def _flows(flows_fw, flows_bw, who):
     if flows_fw.device != flows_bw.device:
         raise RuntimeError(f"{who}: flows_fw is on {flows_fw.device}, flows_bw on {flows_bw.device}")
     return flows_fw.contiguous(), flows_bw.contiguous()
+
+
+def _uint8_maps(who, what, t, shape, dev=None, take_bool=False, refusal=None):
+    """An optional uint8 map of ``shape``, contiguous -- with ``dev``, on the GPU and on the flows' device.  ``take_bool``: a bool
+    map is converted; ``refusal``: the caller's one sentence for a wrong type, dtype or shape."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(refusal or f"{who}: {what}: need a tensor, got {type(t).__name__}")
+    if take_bool and t.dtype == torch.bool:
+        t = t.to(torch.uint8)
+    if t.dtype != torch.uint8 or tuple(t.shape) != shape:
+        raise RuntimeError(refusal or f"{who}: {what}: need {shape} uint8, got {tuple(t.shape)} {t.dtype}")
+    if dev is not None:
+        _lib.require_gpu_tensor(t, f"{who}: {what}")
+        if t.device != dev:
+            raise RuntimeError(f"{who}: {what} is on {t.device}, the flows on {dev}")
+    return t.contiguous()
+
+
+def _guide(who, images_or_grey, shape, dev, of):
+    """Checks a guide for maps of ``shape`` on ``dev``, uint8 frames or a grey fp32 guide of the caller's, and returns it contiguous
+    (:func:`_grey` makes the guide of it); ``of``: what else is on ``dev``, "the disparity" or "the flows"."""
+    t = images_or_grey
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{who}: images: need a tensor, got {type(t).__name__}")
+    colour = t.dtype == torch.uint8
+    if t.dtype not in (torch.uint8, torch.float32) or tuple(t.shape) != (shape + (3,) if colour else shape):
+        raise RuntimeError(f"{who}: images: need channels-last {shape + (3,)} uint8 frames or a grey {shape} float32 guide, got "
+                           f"{tuple(t.shape)} {t.dtype}")
+    _lib.require_gpu_tensor(t, f"{who}: images")
+    if t.device != dev:
+        raise RuntimeError(f"{who}: images are on {t.device}, {of} on {dev}")
+    return t.contiguous()
+
+
+def _grey(guide):
+    return _lib.optflow_grey(guide) if guide.dtype == torch.uint8 else guide
 
 
 def _check_scalars(who, **values):
@@ -288,12 +336,11 @@ def propagate(masks_u8, flows_fw, flows_bw, valid=None, reach=2, return_hits=Fal
     flows_fw, flows_bw = _flows(flows_fw, flows_bw, "propagate")
     if tuple(flows_fw.shape[:3]) != tuple(masks_u8.shape):
         raise RuntimeError(f"propagate: masks {tuple(masks_u8.shape)} do not go with flows {tuple(flows_fw.shape)}")
-    if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (masks_u8.shape[0], 2) + tuple(masks_u8.shape[1:])
-                              or valid.dtype != torch.uint8):
-        raise RuntimeError("propagate: valid: need a (F, 2, H, W) uint8 tensor")
+    valid = _uint8_maps("propagate", "valid", valid, (masks_u8.shape[0], 2) + tuple(masks_u8.shape[1:]),
+                        refusal="propagate: valid: need a (F, 2, H, W) uint8 tensor")
     src = masks_u8.contiguous()
     hits = torch.empty_like(src) if return_hits else None
-    dst = _lib.mask_propagate(src, flows_fw, flows_bw, reach, valid=None if valid is None else valid.contiguous(), hits=hits)
+    dst = _lib.mask_propagate(src, flows_fw, flows_bw, reach, valid=valid, hits=hits)
     return (dst, hits) if return_hits else dst
 
 

@@ -129,26 +129,9 @@ def refine_flow(flows, images_or_grey, valid=None, radius=7, sigma_i=GREY_SIGMA,
         raise RuntimeError(f"{who}: flows: need (P, H, W, 2) float32 with P, H, W >= 1, got {tuple(flows.shape)} {flows.dtype}")
     _lib.require_gpu_tensor(flows, f"{who}: flows")
     shape, dev = tuple(int(v) for v in flows.shape[:3]), flows.device
-    g = images_or_grey
-    if not isinstance(g, torch.Tensor):
-        raise RuntimeError(f"{who}: images: need a tensor, got {type(g).__name__}")
-    colour = g.dtype == torch.uint8
-    if g.dtype not in (torch.uint8, torch.float32) or tuple(g.shape) != (shape + (3,) if colour else shape):
-        raise RuntimeError(f"{who}: images: need channels-last {shape + (3,)} uint8 frames or a grey {shape} float32 guide, got "
-                           f"{tuple(g.shape)} {g.dtype}")
-    _lib.require_gpu_tensor(g, f"{who}: images")
-    if g.device != dev:
-        raise RuntimeError(f"{who}: images are on {g.device}, the flows on {dev}")
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or tuple(valid.shape) != shape:
-            got = f"{tuple(valid.shape)} {valid.dtype}" if isinstance(valid, torch.Tensor) else type(valid).__name__
-            raise RuntimeError(f"{who}: valid: need {shape} uint8, got {got}")
-        _lib.require_gpu_tensor(valid, f"{who}: valid")
-        if valid.device != dev:
-            raise RuntimeError(f"{who}: valid is on {valid.device}, the flows on {dev}")
-        valid = valid.contiguous()
-    grey = _lib.optflow_grey(g.contiguous()) if colour else g.contiguous()
-    return _lib.flow_median(flows.contiguous(), grey, torch.empty(shape + (2,), dtype=torch.float32, device=dev), valid=valid,
+    guide = motion._guide(who, images_or_grey, shape, dev, "the flows")
+    valid = motion._uint8_maps(who, "valid", valid, shape, dev)
+    return _lib.flow_median(flows.contiguous(), motion._grey(guide), torch.empty(shape + (2,), dtype=torch.float32, device=dev), valid=valid,
                             radius=radius, sigma_i=sigma_i, sigma_s=sigma_s, tiled=DEFAULT_MEDIAN_TILED if tiled is None else bool(tiled))
 
 
